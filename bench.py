@@ -10,8 +10,15 @@ contiguous blocks, so N = 1 runs the whole batch and N = 8 runs 128 trees per
 rank.  Metric: site-node-state updates/s = B*L*n_int*Q per step over all
 ranks.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...
+
+A plain run sets up, settles the clocks, warms up, times the K steps and
+prints the headline line.  --dump-outputs DIR also writes what the last timed
+step computed.  --full adds every other measurement to the line: the
+per-kernel roofline of the step, the CPU baseline, the C4 end-to-end and
+shard lines, C2, C3, C5 (both GEMM precisions; at N > 1 the site-sharded C5
+leg), NK and the ragged batch; the --no-* switches drop single ones of them.
 """
 
 from __future__ import annotations
@@ -41,6 +48,11 @@ def parse():
     ap.add_argument("--sites", type=int, default=5000)
     ap.add_argument("--states", type=int, default=4)
     ap.add_argument("--tau", type=float, default=0.5)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beside the headline figure (roofline, CPU "
+                         "baseline, C4 e2e / shard, C2, C3, C5, NK, ragged)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32)")
     ap.add_argument("--no-graph", action="store_true", help="launch eagerly, no hipGraph")
     ap.add_argument("--no-settle", action="store_true",
                     help="skip the clock-settle steps before the warmup (cold-start timing)")
@@ -110,6 +122,25 @@ def host_cpu():
     return info, use
 
 
+DUMP_SAMPLE = 4 << 20  # elements kept of a larger array (16 MB as float32)
+
+
+def dump_outputs(torch, outdir, arrays):
+    """Write each tensor as outdir/<name>.npy in float32.  A tensor of more
+    than DUMP_SAMPLE elements is written as a fixed sample: its elements at
+    sorted flat (row-major) indices from a seeded generator -- the same
+    indices for the same shape, so the dumps of two builds compare element
+    for element."""
+    os.makedirs(outdir, exist_ok=True)
+    for name, t in arrays.items():
+        if t.numel() > DUMP_SAMPLE:
+            flat = np.sort(np.random.default_rng(0).integers(0, t.numel(), size=DUMP_SAMPLE))
+            at = tuple(torch.from_numpy(c).to(t.device)
+                       for c in np.unravel_index(flat, tuple(t.shape)))
+            t = t[at]
+        np.save(os.path.join(outdir, name + ".npy"), t.float().contiguous().cpu().numpy())
+
+
 class Step:
     """fused fwd + adjoint into preallocated buffers (capturable)."""
 
@@ -154,6 +185,46 @@ def time_kernels(torch, step, iters=20):
         torch.cuda.synchronize()
         out[name] = float(np.mean([e0.elapsed_time(e1) for e0, e1 in ev])) * 1e-3
     return out
+
+
+def c4_roofline(torch, step, traffic_json, B, n, L, Q):
+    """The step's kernels against the HBM roofline: event time per launch of
+    the fused, forward and adjoint kernels over their algorithmic bytes, with
+    the PMC-measured bytes of traffic_json where it is keyed by this workload."""
+    n_int = n - 1
+    # per-kernel device time (HIP events) -> roofline of the step's kernel
+    kt = time_kernels(torch, step)
+    nl = n
+    # algorithmic HBM bytes per launch, SURVEY.md section 8(d) / DESIGN.md "Roofline":
+    #   fwd:   int8 leaves in + fp32 DP table out            B*L*(n + 4*Q*n_int)
+    #   bwd:   leaves + DP table in                          B*L*(n + 4*Q*n_int)
+    #   fused: fwd + the adjoint's re-read of both           B*L*(2n + 8*Q*n_int)
+    #   (no site scores are written in this step; dC and tree scores are O(Q^2 + B))
+    fwd_bytes = B * L * (nl + 4 * Q * n_int)
+    kern = {"sankoff_fwd_bwd": (kt["sankoff_fwd_bwd"], 2 * fwd_bytes),
+            "sankoff_fwd": (kt["sankoff_fwd"], fwd_bytes),
+            "sankoff_bwd": (kt["sankoff_bwd"], fwd_bytes)}
+    dom = "sankoff_fwd_bwd"
+    achieved = kern[dom][1] / kern[dom][0] / 1e9
+    # measured HBM traffic per launch (rocprofv3 FETCH_SIZE / WRITE_SIZE passes,
+    # calibrated: tools/pmc.sh traffic c4 -> profiles/traffic.json)
+    traffic = {}
+    try:
+        with open(traffic_json) as f:
+            tj = json.load(f)
+        if tj.get("workload_key") == f"{B}x{n}x{L}x{Q}":
+            traffic = {k: tj.get(k) for k in kern}
+    except (OSError, ValueError):
+        pass
+    per_kernel = {k: {"us": round(v[0] * 1e6, 2), "algorithmic_bytes": v[1],
+                      "GBs": round(v[1] / v[0] / 1e9, 1),
+                      "frac": round(v[1] / v[0] / 1e9 / HBM_PEAK_GBS, 4),
+                      "traffic_bytes": traffic.get(k)} for k, v in kern.items()}
+    return {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 1),
+            "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
+            "traffic": traffic.get(dom),
+            "per_kernel": per_kernel,
+            "per_kernel_us": {k: round(v[0] * 1e6, 2) for k, v in kern.items()}}
 
 
 def shard_line(torch, device, ch, leaves, cost, tau, L, Q, n, Bs):
@@ -870,40 +941,16 @@ def main():
             last = torch.cat([step.out_b["d_cost"].view(-1),
                               step.out_f["tree_score"].sum().view(1)])
         np.save(dump, last.cpu().numpy())
-
-    # per-kernel device time (HIP events) -> roofline of the step's kernel
-    kt = time_kernels(torch, step)
-    nl = n
-    # algorithmic HBM bytes per launch, SURVEY.md section 8(d) / DESIGN.md "Roofline":
-    #   fwd:   int8 leaves in + fp32 DP table out            B*L*(n + 4*Q*n_int)
-    #   bwd:   leaves + DP table in                          B*L*(n + 4*Q*n_int)
-    #   fused: fwd + the adjoint's re-read of both           B*L*(2n + 8*Q*n_int)
-    #   (no site scores are written in this step; dC and tree scores are O(Q^2 + B))
-    fwd_bytes = B * L * (nl + 4 * Q * n_int)
-    kern = {"sankoff_fwd_bwd": (kt["sankoff_fwd_bwd"], 2 * fwd_bytes),
-            "sankoff_fwd": (kt["sankoff_fwd"], fwd_bytes),
-            "sankoff_bwd": (kt["sankoff_bwd"], fwd_bytes)}
-    dom = "sankoff_fwd_bwd"
-    achieved = kern[dom][1] / kern[dom][0] / 1e9
-    # measured HBM traffic per launch (rocprofv3 FETCH_SIZE / WRITE_SIZE passes,
-    # calibrated: tools/pmc.sh traffic c4 -> profiles/traffic.json)
-    traffic = {}
-    try:
-        with open(args.traffic) as f:
-            tj = json.load(f)
-        if tj.get("workload_key") == f"{B}x{n}x{L}x{Q}":
-            traffic = {k: tj.get(k) for k in kern}
-    except (OSError, ValueError):
-        pass
-    per_kernel = {k: {"us": round(v[0] * 1e6, 2), "algorithmic_bytes": v[1],
-                      "GBs": round(v[1] / v[0] / 1e9, 1),
-                      "frac": round(v[1] / v[0] / 1e9 / HBM_PEAK_GBS, 4),
-                      "traffic_bytes": traffic.get(k)} for k, v in kern.items()}
-    roofline = {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 1),
-                "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
-                "traffic": traffic.get(dom),
-                "per_kernel": per_kernel,
-                "per_kernel_us": {k: round(v[0] * 1e6, 2) for k, v in kern.items()}}
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path holds after the last step: the DP
+        # table in the oracle's (B, n_int, Q, L) order whatever the kernel's
+        # layout, the tree scores and dC (rank 0's shard at N > 1, with the
+        # all-reduced [dC, loss] beside them)
+        arrays = {"dp": eng.state_rows(step.out_f["dp"]),
+                  "tree_score": step.out_f["tree_score"], "d_cost": step.out_b["d_cost"]}
+        if dist_on:
+            arrays["reduced"] = reds[(it[0] - 1) % 2]
+        dump_outputs(torch, args.dump_outputs, arrays)
 
     result = {
         "metric": "site-node-state updates/sec (Sankoff fwd+grad)",
@@ -929,11 +976,12 @@ def main():
                    "process_group": dist.get_backend() if dist_on else None,
                    "rccl_ranks": dist_info["rccl_ranks"] if dist_info else None,
                    "world_size": dist_info["world_size"] if dist_info else None},
-        "roofline": roofline,
     }
+    if args.full:
+        result["roofline"] = c4_roofline(torch, step, args.traffic, B, n, L, Q)
     if dist_info:
         result["dist"] = dist_info
-    if rank == 0 and not dist_on:
+    if args.full and rank == 0 and not dist_on:
         hinfo, threads = host_cpu()
         threads = args.cpu_threads or threads
         if not args.no_cpu_baseline:
@@ -960,7 +1008,7 @@ def main():
             result["nk"] = nk_line(torch, device)
         if not args.no_ragged:
             result["ragged"] = ragged_line(torch, device)
-    if dist_on and not args.no_c5:
+    if args.full and dist_on and not args.no_c5:
         result["c5"] = c5_line(torch, device, steps=args.c5_steps, warmup=args.c5_warmup,
                                rank=rank, world=world, nl=args.c5_taxa, L=args.c5_sites,
                                dist_on=True)

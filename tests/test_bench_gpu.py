@@ -78,6 +78,51 @@ def test_bench_world2_device_share_sums_the_whole_batch(tmp_path):
     np.testing.assert_allclose(red[q2], float(f.tree_score.double().sum()), rtol=1e-6)
 
 
+def test_bench_plain_run_is_lean_and_dumps_the_last_step(tmp_path):
+    """A plain ``bench.py --gpus 1 --steps K --warmup W`` prints the headline
+    line only (no roofline, baseline or other-config keys: those need
+    --full), and --dump-outputs writes the last timed step's dp (in
+    (B, n_int, Q, L) order), tree_score and d_cost as float32 -- equal bit
+    for bit to the engine's own over the same seeded batch."""
+    trees, taxa, sites, states, steps = 24, 16, 333, 4, 3
+    out = tmp_path / "dump"
+    cmd = [sys.executable, "bench.py", "--gpus", "1", "--steps", str(steps), "--warmup", "1",
+           "--trees", str(trees), "--taxa", str(taxa), "--sites", str(sites),
+           "--states", str(states), "--dump-outputs", str(out)]
+    r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    res = json.loads(lines[0])
+    assert res["steps"] == steps and res["n_gpus"] == 1 and res["dtype"] == "f32"
+    assert res["higher_is_better"] is True and res["unit"] == "site-node-state updates/s"
+    units = trees * sites * (taxa - 1) * states
+    np.testing.assert_allclose(res["value"], units / (res["ms_per_step"] * 1e-3), rtol=1e-9)
+    for key in ("roofline", "cpu_baseline", "c4_e2e", "c4_shard", "c2", "c3", "c5", "c5_f32",
+                "nk", "ragged"):
+        assert key not in res, key
+    assert sorted(os.listdir(out)) == ["d_cost.npy", "dp.npy", "tree_score.npy"]
+
+    import torch
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    from trex_amd import SankoffEngine
+
+    dev = torch.device("cuda", 0)
+    ch, plan, leaves, cost = bench.make_inputs(torch, dev, trees, taxa, sites, states, 0, trees)
+    eng = SankoffEngine(plan, sites, states, dev)
+    f, dc, _, _ = eng.fwd_bwd(leaves, cost, 0.5)
+    torch.cuda.synchronize()
+    got = {k: np.load(out / f"{k}.npy") for k in ("dp", "tree_score", "d_cost")}
+    assert all(v.dtype == np.float32 for v in got.values())
+    assert got["dp"].shape == (trees, taxa - 1, states, sites)
+    np.testing.assert_array_equal(got["dp"], eng.state_rows(f.dp).cpu().numpy())
+    np.testing.assert_array_equal(got["tree_score"], f.tree_score.cpu().numpy())
+    np.testing.assert_array_equal(got["d_cost"], dc.cpu().numpy())
+
+
 def test_bench_world2_c5_site_shard_matches_single_process():
     """The bench's N > 1 C5 leg (site shard, Gram all-reduce of the ancestor
     rows + mirror, MAX-reduced timer) at a small shape: 128 taxa (255 nodes,
@@ -89,7 +134,7 @@ def test_bench_world2_c5_site_shard_matches_single_process():
     env = dict(os.environ, TREX_BENCH_DEVICE_SHARE="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "bench.py",
-           "--gpus", "2", "--steps", "2", "--warmup", "1", "--trees", "16", "--taxa", "16",
+           "--gpus", "2", "--full", "--steps", "2", "--warmup", "1", "--trees", "16", "--taxa", "16",
            "--sites", "256", "--c5-taxa", str(taxa), "--c5-sites", str(sites),
            "--c5-steps", str(steps), "--c5-warmup", str(warmup)]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
@@ -127,7 +172,7 @@ def test_bench_rccl_one_rank_rehearsal(tmp_path):
     env.pop("TREX_BENCH_DEVICE_SHARE", None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "bench.py",
-           "--gpus", "1", "--steps", str(steps), "--warmup", "1", "--trees", str(trees),
+           "--gpus", "1", "--full", "--steps", str(steps), "--warmup", "1", "--trees", str(trees),
            "--taxa", str(taxa), "--sites", str(sites), "--states", str(states),
            "--c5-taxa", "64", "--c5-sites", "300", "--c5-steps", "3", "--c5-warmup", "1"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)

@@ -3,11 +3,12 @@
 # settings, REPS rounds (default 2) of one bench run per arm:
 #   tools/ab.sh trex_amd/libtrexhip.so trex_amd/libtrex_ab_x.so   (TREX_HIP_LIB per arm)
 #   tools/ab.sh "TREX_GRAM=3" "TREX_GRAM=5"                        (an env assignment per arm)
-# BENCH_ARGS overrides the bench flags (default: the C4 line only).  One line
+# BENCH_ARGS overrides the bench flags (default: the C4 line only; keep --full
+# in it, the per-kernel times and the other lines come only with it).  One line
 # per run: the arm, C4 value (1e9 updates/s), per-kernel us and whichever of
 # the C3 / C5 / NK / shard lines the flags kept.
 cd "$(dirname "$0")/.."
-ARGS=${BENCH_ARGS:---no-cpu-baseline --no-c5 --no-c2 --no-c3 --no-nk --no-ragged --steps 20}
+ARGS=${BENCH_ARGS:---full --no-cpu-baseline --no-c5 --no-c2 --no-c3 --no-nk --no-ragged --steps 20}
 for rep in $(seq ${REPS:-2}); do
   for arm in "$@"; do
     if [[ "$arm" == *=* ]]; then

@@ -17,7 +17,7 @@ mkdir -p "$OUT"
 export TMPDIR=/tmp
 cd /tmp
 if [ "$W" = bench ]; then
-  CMD="python3 $ROOT/bench.py ${BENCH_ARGS:---no-cpu-baseline --no-c2 --no-c3 --no-nk --no-ragged --no-shard --no-e2e --steps 2 --warmup 1 --no-settle}"
+  CMD="python3 $ROOT/bench.py ${BENCH_ARGS:---full --no-cpu-baseline --no-c2 --no-c3 --no-nk --no-ragged --no-shard --no-e2e --steps 2 --warmup 1 --no-settle}"
 else
   CMD="python3 $ROOT/tools/prof.py $W --iters ${ITERS:-3} ${PROF_ARGS:-}"
 fi
