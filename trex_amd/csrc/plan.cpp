@@ -40,8 +40,15 @@ struct Child {
   int index;  // leaf index or internal row
 };
 
+// TREX_DEFER=0 turns the deferred cherry edges off (A/B, tests); read per
+// plan build, so one process can build both kinds
+bool defer_enabled() {
+  const char* e = std::getenv("TREX_DEFER");
+  return !(e && e[0] == '0');
+}
+
 // One tree.  Returns false on a malformed child id.
-bool plan_one_tree(const int32_t* ch, int n_all, int32_t* fwd, int32_t* bt,
+bool plan_one_tree(const int32_t* ch, int n_all, bool defer_on, int32_t* fwd, int32_t* bt,
                    int* n_slots, int* bt_ok, int* n_dag, int* n_unreached) {
   const int nl = (n_all + 1) / 2;
   const int ni = n_all - nl;
@@ -164,11 +171,7 @@ bool plan_one_tree(const int32_t* ch, int n_all, int32_t* fwd, int32_t* bt,
   *n_unreached = unr;
 
   // deferred edges (kChildDeferred): cherries with one reached parent
-  // (TREX_DEFER=0 turns them off, A/B)
-  static const bool defer_on = [] {
-    const char* e = std::getenv("TREX_DEFER");
-    return !(e && e[0] == '0');
-  }();
+  // (defer_on: defer_enabled() of this plan build)
   std::vector<char> deferred(ni, 0);
   if (defer_on)
     for (int c = 0; c < ni; ++c)
@@ -471,10 +474,11 @@ extern "C" int trex_plan_build(const int32_t* children, int B, int n_all,
   int32_t* staged = bt + (int64_t)B * ni * 2;
   int32_t* lanes = staged + (int64_t)B * staged_tree_ints(ni);
   int max_slots = 0, all_bt_ok = 1, dag = 0, unr = 0, lp_slots = 0;
+  const bool defer_on = defer_enabled();
   for (int b = 0; b < B; ++b) {
     int s = 0, ok = 0, d = 0, u = 0;
-    if (!plan_one_tree(children + (int64_t)b * n_all * 2, n_all, fwd + (int64_t)b * ni * 4,
-                       bt + (int64_t)b * ni * 2, &s, &ok, &d, &u))
+    if (!plan_one_tree(children + (int64_t)b * n_all * 2, n_all, defer_on,
+                       fwd + (int64_t)b * ni * 4, bt + (int64_t)b * ni * 2, &s, &ok, &d, &u))
       return set_error(TREX_E_TOPOLOGY, "trex_plan_build: tree %d has an invalid child list", b);
     stage_one_tree(children + (int64_t)b * n_all * 2, n_all, staged + b * staged_tree_ints(ni));
     const int ls = lane_program_one_tree(children + (int64_t)b * n_all * 2, n_all,
@@ -550,13 +554,14 @@ extern "C" int trex_ragged_plan_build(const int32_t* children, const int32_t* n_
   std::memset(plan, 0, sizeof(int32_t) * TREX_PLAN_HEADER_INTS);
   int64_t step_off = 0, item_off = 0, site_off = 0, leaf_off = 0, rows_off = 0, child_off = 0;
   int max_slots = 0, max_nl = 0, max_ni = 0, all_ok = 1, dag = 0, unr = 0;
+  const bool defer_on = defer_enabled();
   for (int b = 0; b < B; ++b) {
     const int na = n_all[b];
     const int nl = (na + 1) / 2;
     const int ni = na - nl;
     int s = 0, ok = 0, d = 0, u = 0;
-    if (!plan_one_tree(children + child_off, na, fwd + step_off * 4, bt + step_off * 2, &s, &ok, &d,
-                       &u))
+    if (!plan_one_tree(children + child_off, na, defer_on, fwd + step_off * 4, bt + step_off * 2,
+                       &s, &ok, &d, &u))
       return set_error(TREX_E_TOPOLOGY, "trex_ragged_plan_build: tree %d has an invalid child list",
                        b);
     if (site_off > 0x7FFFFFFF)

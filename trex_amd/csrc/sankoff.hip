@@ -426,6 +426,45 @@ __device__ __forceinline__ void message(const Coef<Q>& cf, float a, float bcoef,
   }
 }
 
+// factored-softmin edge adjoint in two halves.  softk_weights: what depends
+// on the child's D alone (u_j = exp((min D - D_j)/tau), 1 / s_i, s = K u);
+// softk_edge: the parent cotangent applied to them.  A deferred cherry's D is
+// a function of its two leaf codes, so its first half is a table lookup
+// (TREX_PAIR_TABLES).
+template <int Q, bool SYM>
+__device__ __forceinline__ void softk_weights(const Coef<Q>& cf, float a, const float (&d)[Q],
+                                              float (&u)[Q], float (&rs)[Q]) {
+  float md = d[0];
+#pragma unroll
+  for (int j = 1; j < Q; ++j) md = fminf(md, d[j]);
+  const float mda = md * a;
+#pragma unroll
+  for (int j = 0; j < Q; ++j) u[j] = fast_exp2(fmaf(-d[j], a, mda));
+  float sv[Q];
+  kvec<Q, SYM>(cf, u, sv);
+#pragma unroll
+  for (int i = 0; i < Q; ++i) rs[i] = __builtin_amdgcn_rcpf(sv[i]);
+}
+
+template <int Q>
+__device__ __forceinline__ void softk_edge(const Coef<Q>& cf, const float (&u)[Q],
+                                           const float (&rs)[Q], const float (&g)[Q],
+                                           float (&acc)[Q][Q], float (&gc)[Q]) {
+  float r[Q];
+#pragma unroll
+  for (int i = 0; i < Q; ++i) r[i] = g[i] * rs[i];
+#pragma unroll
+  for (int i = 0; i < Q; ++i) axpy<Q>(acc[i], r[i], u);
+  // t[j] = sum_i r_i K[i][j] (row pairs of K), gc = u * t
+  float t[Q];
+#pragma unroll
+  for (int j = 0; j < Q; ++j) t[j] = r[0] * cf.k[0][j];
+#pragma unroll
+  for (int i = 1; i < Q; ++i) axpy<Q>(t, r[i], cf.k[i]);
+#pragma unroll
+  for (int j = 0; j < Q; ++j) gc[j] = u[j] * t[j];
+}
+
 // --------------------------------------------------------------------------
 // adjoint of one child message: acc[i][j] += gbar[i] w[i][j];
 // gc[j] = sum_i gbar[i] w[i][j]   (w = tie-averaged argmin or softmax weights)
@@ -464,28 +503,16 @@ __device__ __forceinline__ void message_adjoint(const Coef<Q>& cf, float a,
         }
       }
     } else if constexpr (MODE == kSoftK) {
-      float md = d[0][s];
+      float ds[Q], gs[Q], u[Q], rs[Q], gcs[Q];
 #pragma unroll
-      for (int j = 1; j < Q; ++j) md = fminf(md, d[j][s]);
-      const float mda = md * a;
-      float u[Q];
+      for (int j = 0; j < Q; ++j) {
+        ds[j] = d[j][s];
+        gs[j] = g[j][s];
+      }
+      softk_weights<Q, SYM>(cf, a, ds, u, rs);
+      softk_edge<Q>(cf, u, rs, gs, acc, gcs);
 #pragma unroll
-      for (int j = 0; j < Q; ++j) u[j] = fast_exp2(fmaf(-d[j][s], a, mda));
-      float r[Q];
-      float sv[Q];
-      kvec<Q, SYM>(cf, u, sv);
-#pragma unroll
-      for (int i = 0; i < Q; ++i) r[i] = g[i][s] * __builtin_amdgcn_rcpf(sv[i]);
-#pragma unroll
-      for (int i = 0; i < Q; ++i) axpy<Q>(acc[i], r[i], u);
-      // t[j] = sum_i r_i K[i][j] (row pairs of K), gc = u * t
-      float t[Q];
-#pragma unroll
-      for (int j = 0; j < Q; ++j) t[j] = r[0] * cf.k[0][j];
-#pragma unroll
-      for (int i = 1; i < Q; ++i) axpy<Q>(t, r[i], cf.k[i]);
-#pragma unroll
-      for (int j = 0; j < Q; ++j) gc[j][s] = u[j] * t[j];
+      for (int j = 0; j < Q; ++j) gc[j][s] = gcs[j];
     } else {
 #pragma unroll
       for (int j = 0; j < Q; ++j) gc[j][s] = 0.0f;
@@ -600,8 +627,29 @@ struct KArgs {
 // first reverse step (always the root's), before any child cotangent is
 // written, and slots are lane-private (a dedicated root slot cost 1 KiB per
 // wave: 24 -> 29 waves per CU at C4's 3 slots).
-constexpr int kTabFloats = 128;
+//
+// Pair tables (TREX_PAIR_TABLES): a deferred cherry's D is T[c0] + T[c1], a
+// function of its two leaf codes, so everything the sweeps compute from it is
+// one of (Q + 1)^2 <= 25 vectors, indexed p = c0 (Q + 1) + c1: TM[p][i] its
+// message to the parent (every mode), TU[p][j] / TR[p][i] the u_j and 1 / s_i
+// of the parent -> cherry edge adjoint (factored softmin).  Built once per
+// wave from the same helpers the lanes run, so a lookup is bitwise what the
+// lane would compute.  Adjoint-bearing kernels keep them after the leaf tables
+// (1 200 B more per wave, their occupancy comes from their registers); the
+// forward-only kernel (LDS-bound at C4) has no W and keeps TM over its region,
+// at kPairFwd, so its LDS is unchanged.
+#ifndef TREX_PAIR_TABLES
+#define TREX_PAIR_TABLES 1  // 0: cherries compute their message / edge weights per site
+#endif
+constexpr bool kPairTables = TREX_PAIR_TABLES != 0;
+constexpr int kLeafTabFloats = 128;
 constexpr int kWTab = 32;  // (Q + 1) Q <= 20 message floats precede the weights
+constexpr int kPairFloats = 100;  // (Q + 1)^2 Q at Q = 4
+constexpr int kPairFwd = 28;      // forward-only: TM at [28, 128)
+// table floats ahead of the slot stack
+constexpr int tab_floats(int phase) {
+  return kLeafTabFloats + ((kPairTables && phase != 1) ? 3 * kPairFloats : 0);
+}
 #ifndef TREX_ADJ_RING
 #define TREX_ADJ_RING 3
 #endif
@@ -651,7 +699,12 @@ __device__ __forceinline__ void sankoff_body(const KArgs& A, float* lds) {
   load_coef<Q, MODE>(A.cost, a, cf);
 
   float* tab = lds;
-  float* slots = lds + kTabFloats;
+  float* slots = lds + tab_floats(PHASE);
+  // pair tables (see the LDS map)
+  float* tm = tab + (PHASE == 1 ? kPairFwd : kLeafTabFloats);
+  float* tu = tab + kLeafTabFloats + kPairFloats;
+  float* tr = tab + kLeafTabFloats + 2 * kPairFloats;
+  constexpr bool PAIR_ADJ = kPairTables && BWD && MODE == kSoftK;
   constexpr int kRootSlot = 0;
   int8_t* lleaf = reinterpret_cast<int8_t*>(slots + (size_t)max(A.n_slots, 1) * Q * kWave * SPT);
 
@@ -690,13 +743,44 @@ __device__ __forceinline__ void sankoff_body(const KArgs& A, float* lds) {
         }
       } else {
         message<Q, 1, MODE>(cf, a, bcoef, d1, m1);
-        message_adjoint<Q, 1, MODE>(cf, a, d1, g1, w1, gc1);
+        if constexpr (BWD) message_adjoint<Q, 1, MODE>(cf, a, d1, g1, w1, gc1);
       }
 #pragma unroll
       for (int i = 0; i < Q; ++i) {
         tab[lane * Q + i] = m1[i][0];
+        if constexpr (BWD) {  // the forward-only kernel has no W (TM lies there)
 #pragma unroll
-        for (int j = 0; j < Q; ++j) tab[kWTab + (lane * Q + i) * Q + j] = w1[i][j];
+          for (int j = 0; j < Q; ++j) tab[kWTab + (lane * Q + i) * Q + j] = w1[i][j];
+        }
+      }
+    }
+  }
+  // ---- once per wave: the pair tables.  Lane p < (Q + 1)^2 builds entry
+  // p = c0 (Q + 1) + c1 from D = T[c0] + T[c1] (the forward's order) with the
+  // per-site helpers ----
+  if constexpr (kPairTables) {
+    __syncthreads();  // T is written by lanes <= Q
+    if (lane < (Q + 1) * (Q + 1)) {
+      const int c0 = lane / (Q + 1), c1 = lane - c0 * (Q + 1);
+      float t0[Q], t1[Q], d1[Q][1];
+      lds_vec_get<Q>(tab + c0 * Q, t0);
+      lds_vec_get<Q>(tab + c1 * Q, t1);
+#pragma unroll
+      for (int j = 0; j < Q; ++j) d1[j][0] = t0[j] + t1[j];
+      if constexpr (FWD) {
+        float m1[Q][1], mv[Q];
+        message<Q, 1, MODE, false>(cf, a, bcoef, d1, m1);
+#pragma unroll
+        for (int i = 0; i < Q; ++i) mv[i] = m1[i][0];
+        lds_vec_put<Q>(tm + lane * Q, mv);
+      }
+      if constexpr (PAIR_ADJ) {
+        float ds[Q], u[Q], rs[Q];
+#pragma unroll
+        for (int j = 0; j < Q; ++j) ds[j] = d1[j][0];
+        softk_weights<Q, SYM>(cf, a, ds, u, rs);
+        lds_vec_put<Q>(tu + lane * Q, u);
+        lds_vec_put<Q>(tr + lane * Q, rs);
       }
     }
   }
@@ -801,6 +885,9 @@ __device__ __forceinline__ void sankoff_body(const KArgs& A, float* lds) {
         if (k + 1 < n_int) nxt = load_step(prog, k + 1);
         // gather both children (LDS reads in flight together)
         float d[2][Q][SPT];
+        int pair[SPT];  // c0 (Q + 1) + c1 of a step whose children are both codes
+#pragma unroll
+        for (int s = 0; s < SPT; ++s) pair[s] = 0;
 #pragma unroll
         for (int c = 0; c < 2; ++c) {
           const int desc = c == 0 ? stp.y : stp.z;
@@ -826,6 +913,7 @@ __device__ __forceinline__ void sankoff_body(const KArgs& A, float* lds) {
               lds_vec_get<Q>(tab + code[s] * Q, r);
 #pragma unroll
               for (int i = 0; i < Q; ++i) d[c][i][s] = r[i];  // already the message
+              if constexpr (kPairTables) pair[s] = c == 0 ? code[s] * (Q + 1) : pair[s] + code[s];
             }
           }
         }
@@ -833,7 +921,8 @@ __device__ __forceinline__ void sankoff_body(const KArgs& A, float* lds) {
         for (int c = 0; c < 2; ++c) {
           const int desc = c == 0 ? stp.y : stp.z;
           float m[Q][SPT];
-          if (((desc >> 24) & 3) != kKindInt) {
+          // a deferred cherry handed its message on (TM), not its D
+          if (((desc >> 24) & 3) != kKindInt || (kPairTables && (desc & kChildDeferred))) {
 #pragma unroll
             for (int i = 0; i < Q; ++i)
 #pragma unroll
@@ -871,6 +960,16 @@ __device__ __forceinline__ void sankoff_body(const KArgs& A, float* lds) {
         else
           bst_row<Q, SPT, BWD ? kAuxFusedRow : kAuxFwdRow>(rdp, voff, row * rowbytes, dv);
 #endif
+        if (kPairTables && (stp.w & kStepDeferredIn)) {
+          // the row is stored; its one parent takes the message from the table
+#pragma unroll
+          for (int s = 0; s < SPT; ++s) {
+            float r[Q];
+            lds_vec_get<Q>(tm + pair[s] * Q, r);
+#pragma unroll
+            for (int i = 0; i < Q; ++i) dv[i][s] = r[i];
+          }
+        }
         if (!(stp.w & kStepToNext) && oslot != 0xFF) {
           lds_put<Q, SPT>(slots, oslot, lane, dv);
         }
@@ -965,25 +1064,51 @@ __device__ __forceinline__ void sankoff_body(const KArgs& A, float* lds) {
           }
         };
         if (stp.w & kStepDeferredIn) {
-          // g is the parent's cotangent: this cherry's D is the sum of its two
-          // leaf messages (the forward's order, so bit-identical), then the
-          // parent -> cherry edge adjoint the parent's step skipped
-          float dc[Q][SPT];
+          // g is the parent's cotangent: this step runs the parent -> cherry
+          // edge adjoint the parent's step skipped
+          float gc[Q][SPT];
+          if constexpr (PAIR_ADJ) {
+            // the edge's u and 1 / s depend on the two leaf codes only
+            int pair[SPT];
 #pragma unroll
-          for (int c = 0; c < 2; ++c) {
-            const int desc = c == 0 ? stp.y : stp.z;
-            int code[SPT];
-            leaf_codes(desc, (desc >> 24) & 3, code);
+            for (int c = 0; c < 2; ++c) {
+              const int desc = c == 0 ? stp.y : stp.z;
+              int code[SPT];
+              leaf_codes(desc, (desc >> 24) & 3, code);
+#pragma unroll
+              for (int s = 0; s < SPT; ++s)
+                pair[s] = c == 0 ? code[s] * (Q + 1) : pair[s] + code[s];
+            }
 #pragma unroll
             for (int s = 0; s < SPT; ++s) {
-              float r[Q];
-              lds_vec_get<Q>(tab + code[s] * Q, r);
+              float u[Q], rs[Q], gs[Q], gcs[Q];
+              lds_vec_get<Q>(tu + pair[s] * Q, u);
+              lds_vec_get<Q>(tr + pair[s] * Q, rs);
 #pragma unroll
-              for (int i = 0; i < Q; ++i) dc[i][s] = (c == 0) ? r[i] : dc[i][s] + r[i];
+              for (int i = 0; i < Q; ++i) gs[i] = g[i][s];
+              softk_edge<Q>(cf, u, rs, gs, acc, gcs);
+#pragma unroll
+              for (int j = 0; j < Q; ++j) gc[j][s] = gcs[j];
             }
+          } else {
+            // the cherry's D is the sum of its two leaf messages (the
+            // forward's order, so bit-identical)
+            float dc[Q][SPT];
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+              const int desc = c == 0 ? stp.y : stp.z;
+              int code[SPT];
+              leaf_codes(desc, (desc >> 24) & 3, code);
+#pragma unroll
+              for (int s = 0; s < SPT; ++s) {
+                float r[Q];
+                lds_vec_get<Q>(tab + code[s] * Q, r);
+#pragma unroll
+                for (int i = 0; i < Q; ++i) dc[i][s] = (c == 0) ? r[i] : dc[i][s] + r[i];
+              }
+            }
+            message_adjoint<Q, SPT, MODE, SYM>(cf, a, dc, g, acc, gc);
           }
-          float gc[Q][SPT];
-          message_adjoint<Q, SPT, MODE, SYM>(cf, a, dc, g, acc, gc);
 #pragma unroll
           for (int i = 0; i < Q; ++i)
 #pragma unroll
@@ -1287,9 +1412,9 @@ int check_shape(const char* fn, int B, int L, int n_all, int Q, Shape* sh) {
 
 int tiles_for(int L, int spt) { return (L + kWave * spt - 1) / (kWave * spt); }
 
-size_t lds_bytes(int n_slots, int nl, int Q, int spt) {
-  const size_t b = (size_t)kTabFloats * 4 + (size_t)std::max(n_slots, 1) * Q * kWave * spt * 4 +
-                   (size_t)nl * kWave * spt;
+size_t lds_bytes(int n_slots, int nl, int Q, int spt, int phase) {
+  const size_t b = (size_t)tab_floats(phase) * 4 +
+                   (size_t)std::max(n_slots, 1) * Q * kWave * spt * 4 + (size_t)nl * kWave * spt;
   return (b + 15) & ~(size_t)15;
 }
 
@@ -1512,7 +1637,7 @@ int run_phase(const char* fn, int phase, const int32_t* plan, int n_slots, const
   if ((int64_t)s.ni * L * Q * 4 > 0x7FFFFFF0LL)
     return set_error(TREX_E_UNSUPPORTED, "%s: one tree's DP table exceeds 2 GiB", fn);
   const int tiles = tiles_for(L, 1);
-  const size_t lds = lds_bytes(n_slots, s.nl, Q, 1);
+  const size_t lds = lds_bytes(n_slots, s.nl, Q, 1, phase);
   if (lds > 65536) return set_error(TREX_E_UNSUPPORTED, "%s: LDS stack too deep", fn);
   if ((int64_t)B * tiles > 0x7FFFFFFF) return set_error(TREX_E_ARG, "%s: grid too large", fn);
   KArgs A;
@@ -1735,7 +1860,7 @@ extern "C" int trex_sankoff_ragged(int phase, const int32_t* plan, int B, int n_
     if (Q > kWideMaxQ) return bigq_ragged_run(fn, c, meta, meta + (size_t)B * kRaggedMeta, items);
     return wide_ragged_run(fn, c, meta, meta + (size_t)B * kRaggedMeta, items);
   }
-  const size_t lds = lds_bytes(n_slots, max_nl, Q, 1);
+  const size_t lds = lds_bytes(n_slots, max_nl, Q, 1, phase);
   if (lds > 65536) return set_error(TREX_E_UNSUPPORTED, "%s: LDS stack too deep", fn);
   KArgs A;
   const int* meta = plan + TREX_PLAN_HEADER_INTS;

@@ -23,8 +23,9 @@ constexpr int32_t kChildPrev = 1 << 27;
 // child is a cherry (both of its children leaves / 1e5 rows) with one
 // parent.  The parent's step hands its own cotangent to the child's slot
 // (or the bypass) instead of the child's, reading no DP row; the child's step
-// (kStepDeferredIn) recomputes its D from its leaf messages and runs the edge
-// adjoint first.  A cherry's row is then never re-read from HBM.
+// (kStepDeferredIn) recomputes its D from its leaf messages (or looks the
+// edge's weights up by its two leaf codes, sankoff.hip pair tables) and runs
+// the edge adjoint first.  A cherry's row is then never re-read from HBM.
 constexpr int32_t kChildDeferred = 1 << 28;
 // forward-step flags (word 3)
 constexpr int32_t kStepRoot = 1;
