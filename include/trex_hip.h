@@ -527,6 +527,59 @@ int trex_sankoff_ragged_backtrack(const int32_t* plan, int B, int64_t items, int
                                   int8_t* anc_states, void* stream);
 
 /* ========================================================================
+ * NNI neighbour scores (no counterpart in the reference, which scores one
+ * tree per run_sankoff call, src/trex/sankoff.py:114-188): the plain score of
+ * all 2 (n_leaves - 2) nearest-neighbour interchanges of every tree from the
+ * DP table of one forward, by a pre-order "outside" pass and an O(Q^2)
+ * evaluation per site and neighbour.  One tree, one site; (+) = min for
+ * tau = 0, smin_tau for tau > 0; D_x = node x's inside row (leaf: 0 at its
+ * code, 1e5 elsewhere; internal: its DP-table row):
+ *   M_x[i]    = (+)_j (C[i][j] + D_x[j])
+ *   O_root    = 0;  O_c[j] = (+)_i (C[i][j] + O_p[i] + M_s[i])   (p = c's
+ *               parent, s = c's sibling); (+)_i (O_v[i] + D_v[i]) is the
+ *               site score at every internal v
+ *   move (v, k), v internal and not the root, u its parent, s its sibling,
+ *               (a0, a1) = children[v] in stored order: a_k and s swap
+ *               places (v: {s, a_(1-k)}, u: {a_k, v});  site score =
+ *               (+)_i (O_u[i] + M_(a_k)[i] + M(M_s + M_(a_(1-k)))[i])
+ * The calls take no flags: the scores are those of the plain score
+ * (site score = (+) D_root).  TREX_FLAG_HARD_ROOT with tau > 0 mixes two
+ * semirings -- min at the root over smin messages -- and a score of that
+ * form cannot be re-rooted at another edge, so it has no outside rows.
+ *
+ * trex_nni_plan_build [host]: children as for trex_plan_build, but only
+ *   proper rooted binary trees are accepted -- every internal node has two
+ *   distinct children with ids below its own, every node but the root
+ *   n_all - 1 exactly one parent, n_leaves >= 3; anything else (-1 fills,
+ *   forward references, shared or orphan rows) is TREX_E_TOPOLOGY.
+ *   nni_plan: int32 buffer of trex_nni_plan_ints(B, n_all) ints (copy it to
+ *   the device unchanged): header [TREX_PLAN_HEADER_INTS] (magic, B, n_all,
+ *   n_leaves, n_int), then per tree the internal rows in pre-order [n_int][4]
+ *   = {row, parent row (-1: root), sibling descriptor, 0} and the moves
+ *   [n_int - 1][4], entry e for v = n_leaves + e: {u row, a0, a1, s
+ *   descriptors}; descriptor = kind << 24 | index (1: leaf index, 2:
+ *   internal row).
+ * ====================================================================== */
+int64_t trex_nni_plan_ints(int B, int n_all);
+int trex_nni_plan_build(const int32_t* children, int B, int n_all, int32_t* nni_plan);
+/* Outside table: outside fp32 in dp's layout [B][n_int][L][Q] (root row
+ * zeros), from dp = the table of trex_sankoff_fwd at the same tau.  Q <= 20
+ * (Q = 2, 3, 4: rows in registers; 4 < Q <= 20: one padded path); larger Q
+ * returns TREX_E_UNSUPPORTED. */
+int trex_sankoff_outside(const int32_t* nni_plan, const int8_t* leaves, const float* cost, int B,
+                         int L, int n_all, int Q, float tau, const float* dp, float* outside,
+                         void* stream);
+/* Neighbour scores: nni_score fp32 [B][n_int - 1][2], entry [b][v - n_leaves][k]
+ * = the tree score after move (v, k): the site scores summed in fp64 in a
+ * fixed order and rounded to fp32, as tree_score is (per-wave partials in
+ * workspace, >= trex_nni_workspace_bytes bytes, no initialisation needed;
+ * repeated calls are bitwise equal).  dp / outside are read as given. */
+int64_t trex_nni_workspace_bytes(int B, int L, int n_all, int Q);
+int trex_sankoff_nni(const int32_t* nni_plan, const int8_t* leaves, const float* cost, int B,
+                     int L, int n_all, int Q, float tau, const float* dp, const float* outside,
+                     float* nni_score, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ========================================================================
  * Synthetic data on the device: trex's
  * generate_groundtruth (src/trex/ground_truth.py:112-197, mutate :20-52) and
  * iid uniform leaf states, from a counter-based generator (splitmix64 of

@@ -3,7 +3,8 @@
 //   * trex_amd/csrc/plan.cpp -- the topology planner (uniform and ragged
 //     batches) on random, quirky (-1 fills, forward references, DAGs,
 //     orphans), cyclic and malformed child lists, writing into buffers sized
-//     exactly by trex_plan_ints / trex_ragged_plan_ints;
+//     exactly by trex_plan_ints / trex_ragged_plan_ints, and the NNI planner
+//     (trex_nni_plan_build) on the same trees, its accepted plans range-checked;
 //   * oracle/cpu_port.c -- the OpenMP C restatement (the CPU baseline and a
 //     test checker) on random trees, Q = 2..20, hard and softmin, with and
 //     without the DP table output.
@@ -97,6 +98,59 @@ int check_uniform() {
   return 0;
 }
 
+// the NNI planner accepts proper binary trees only: every perturbed tree is
+// either refused or still proper, and an accepted plan's words stay in range
+int check_nni() {
+  int built = 0, refused = 0;
+  for (int it = 0; it < 400; ++it) {
+    const int nl = rnd(2, 128);
+    const int n_all = 2 * nl - 1;
+    const int ni = n_all - nl;
+    const int B = rnd(1, 6);
+    std::vector<int32_t> ch((size_t)B * n_all * 2);
+    bool clean = true;
+    for (int b = 0; b < B; ++b) {
+      random_tree(nl, ch.data() + (size_t)b * n_all * 2);
+      if (it % 2) {
+        const int mode = rnd(0, 4);
+        perturb(nl, ch.data() + (size_t)b * n_all * 2, mode);
+        clean = clean && mode == 4;
+      }
+    }
+    const int64_t n = trex_nni_plan_ints(B, n_all);
+    if (n <= 0) return 5;
+    std::vector<int32_t> plan((size_t)n);
+    const int rc = trex_nni_plan_build(ch.data(), B, n_all, plan.data());
+    if (rc != 0 && rc != TREX_E_TOPOLOGY && rc != TREX_E_ARG) return 6;
+    if (clean && nl >= 3 && rc != 0) return 7;  // a coalescent tree is proper
+    if (nl < 3 && rc == 0) return 8;
+    if (rc != 0) {
+      ++refused;
+      continue;
+    }
+    ++built;
+    for (int b = 0; b < B; ++b) {
+      const int32_t* r = plan.data() + TREX_PLAN_HEADER_INTS + (size_t)b * (8 * ni - 4);
+      auto desc_ok = [&](int32_t d) {
+        const int kind = d >> 24, idx = d & 0xFFFF;
+        return (kind == 1 && idx < nl) || (kind == 2 && idx < ni);
+      };
+      if (r[0] != ni - 1 || r[1] != -1) return 9;  // pre-order starts at the root
+      for (int k = 1; k < ni; ++k)
+        if (r[4 * k] < 0 || r[4 * k] >= ni || r[4 * k + 1] <= r[4 * k] || r[4 * k + 1] >= ni ||
+            !desc_ok(r[4 * k + 2]))
+          return 10;
+      const int32_t* mv = r + 4 * ni;
+      for (int e = 0; e < ni - 1; ++e)
+        if (mv[4 * e] <= e || mv[4 * e] >= ni || !desc_ok(mv[4 * e + 1]) ||
+            !desc_ok(mv[4 * e + 2]) || !desc_ok(mv[4 * e + 3]))
+          return 11;
+    }
+  }
+  std::printf("nni plans: %d built, %d refused\n", built, refused);
+  return 0;
+}
+
 int check_ragged() {
   for (int it = 0; it < 200; ++it) {
     const int B = rnd(1, 8);
@@ -159,6 +213,7 @@ int main() {
   if (int e = check_uniform()) return e;
   if (int e = check_ragged()) return e;
   if (int e = check_cpu_port()) return e;
+  if (int e = check_nni()) return e;
   std::printf("sanitize ok\n");
   return 0;
 }

@@ -16,8 +16,10 @@ from .sankoff import (  # noqa: F401
     vectorized_dp,
     vmapped_backtrack,
 )
+from .search import HillClimbResult, nni_hill_climb  # noqa: F401
 from .topology import (  # noqa: F401
     TreePlan,
+    apply_nni,
     children_from_adjacency,
     create_balanced_binary_tree,
     random_topologies,
@@ -27,5 +29,6 @@ __all__ = [
     "LIB_PATH", "TrexError", "lib", "SankoffEngine", "leaf_codes", "run_sankoff", "run_dp",
     "vectorized_dp", "backtrack_sankoff_jit", "vmapped_backtrack",
     "sankoff_value_and_grad", "TreePlan", "children_from_adjacency",
-    "create_balanced_binary_tree", "random_topologies",
+    "create_balanced_binary_tree", "random_topologies", "apply_nni", "nni_hill_climb",
+    "HillClimbResult",
 ]

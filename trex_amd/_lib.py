@@ -45,6 +45,13 @@ SIGNATURES = {
     "trex_sankoff_backtrack": (_c_i, [_p, _c_i, _p, _p, _c_i, _c_i, _c_i, _c_i, _p, _p]),
     "trex_dp_to_trex_layout": (_c_i, [_p, _p, _c_i, _c_i, _c_i, _c_i, _p, _p]),
     "trex_dp_site_major": (_c_i, [_c_i]),
+    # NNI neighbour scores (outside pass + per-edge evaluation)
+    "trex_nni_plan_ints": (_c_i64, [_c_i, _c_i]),
+    "trex_nni_plan_build": (_c_i, [_p, _c_i, _c_i, _p]),
+    "trex_sankoff_outside": (_c_i, [_p, _p, _p, _c_i, _c_i, _c_i, _c_i, _c_f, _p, _p, _p]),
+    "trex_nni_workspace_bytes": (_c_i64, [_c_i, _c_i, _c_i, _c_i]),
+    "trex_sankoff_nni": (_c_i, [_p, _p, _p, _c_i, _c_i, _c_i, _c_i, _c_f, _p, _p, _p, _p, _c_i64,
+                                _p]),
     # multi-GPU exchange (RCCL, dlopen'ed on first use)
     "trex_comm_unique_id_bytes": (_c_i, []),
     "trex_comm_get_unique_id": (_c_i, [_p]),

@@ -615,3 +615,107 @@ extern "C" int trex_ragged_plan_build(const int32_t* children, const int32_t* n_
   }
   return TREX_OK;
 }
+
+// ---------------------------------------------------------------------------
+// NNI plan (sankoff_nni.hip): the pre-order "outside" pass and the per-edge
+// neighbour scores.  Layout (ints): header [16] | per tree a region of
+// nni_tree_ints(ni) ints: pre-order entries [ni][4] | move entries
+// [ni - 1][4].
+//   pre-order entry: {internal row, parent row (-1: the root), sibling
+//     descriptor, 0}; a DFS from the root, so a node's parent comes before it
+//   move entry e (v = n_leaves + e, never the root): {u row, a0 descriptor,
+//     a1 descriptor, s descriptor}: u = v's parent, (a0, a1) = children[v] in
+//     stored order, s = v's sibling
+//   descriptor: kind << 24 | index (kind 1: leaf index, 2: internal row)
+// Only proper rooted binary trees have neighbours: everything trex's child
+// rule tolerates beyond them (-1 fills, forward references, shared or orphan
+// rows) is refused with TREX_E_TOPOLOGY.
+// ---------------------------------------------------------------------------
+namespace trex {
+namespace {
+constexpr int32_t kNniMagic = 0x54524E4E;  // 'TRNN'
+inline int64_t nni_tree_ints(int ni) { return 8LL * ni - 4; }
+
+// nullptr when the tree is a proper rooted binary tree, else what is wrong
+const char* nni_one_tree(const int32_t* ch, int n_all, int32_t* region) {
+  const int nl = (n_all + 1) / 2;
+  const int ni = n_all - nl;
+  std::vector<int> parent(n_all, -1);
+  for (int node = nl; node < n_all; ++node) {
+    const int c0 = ch[2 * node], c1 = ch[2 * node + 1];
+    if (c0 < 0 || c1 < 0) return "a child is missing (-1 fill)";
+    if (c0 >= node || c1 >= node) return "a child id is not below its parent's";
+    if (c0 == c1) return "a node lists the same child twice";
+    if (parent[c0] >= 0 || parent[c1] >= 0) return "a node has two parents";
+    parent[c0] = node;
+    parent[c1] = node;
+  }
+  // 2 ni child slots, all distinct, over the n_all - 1 = 2 ni nodes below the
+  // root: every one of them has exactly one parent, of a higher id, so every
+  // path leads up to the root n_all - 1
+  auto desc = [&](int c) -> int32_t {
+    return c < nl ? (c | (kKindLeaf << 24)) : ((c - nl) | (kKindInt << 24));
+  };
+  auto sibling = [&](int c) {
+    const int p = parent[c];
+    return ch[2 * p] == c ? ch[2 * p + 1] : ch[2 * p];
+  };
+  int32_t* pre = region;
+  int32_t* mv = region + 4LL * ni;
+  std::vector<int> st;
+  st.push_back(n_all - 1);
+  int w = 0;
+  while (!st.empty()) {
+    const int node = st.back();
+    st.pop_back();
+    pre[4 * w] = node - nl;
+    pre[4 * w + 1] = node == n_all - 1 ? -1 : parent[node] - nl;
+    pre[4 * w + 2] = node == n_all - 1 ? 0 : desc(sibling(node));
+    pre[4 * w + 3] = 0;
+    ++w;
+    for (int k = 1; k >= 0; --k)
+      if (ch[2 * node + k] >= nl) st.push_back(ch[2 * node + k]);
+  }
+  if (w != ni) return "an internal node is not reachable from the root";
+  for (int e = 0; e < ni - 1; ++e) {
+    const int v = nl + e;
+    mv[4 * e] = parent[v] - nl;
+    mv[4 * e + 1] = desc(ch[2 * v]);
+    mv[4 * e + 2] = desc(ch[2 * v + 1]);
+    mv[4 * e + 3] = desc(sibling(v));
+  }
+  return nullptr;
+}
+}  // namespace
+}  // namespace trex
+
+extern "C" int64_t trex_nni_plan_ints(int B, int n_all) {
+  if (B <= 0 || n_all < 3 || n_all > 65535) return 0;
+  const int ni = n_all - (n_all + 1) / 2;
+  return TREX_PLAN_HEADER_INTS + (int64_t)B * trex::nni_tree_ints(ni);
+}
+
+extern "C" int trex_nni_plan_build(const int32_t* children, int B, int n_all, int32_t* nni_plan) {
+  using namespace trex;
+  if (!children || !nni_plan || B <= 0 || n_all < 3 || n_all > 65535 || n_all % 2 == 0)
+    return set_error(TREX_E_ARG, "trex_nni_plan_build: bad arguments (B=%d n_all=%d)", B, n_all);
+  const int nl = (n_all + 1) / 2;
+  const int ni = n_all - nl;
+  if (nl < 3)
+    return set_error(TREX_E_TOPOLOGY, "trex_nni_plan_build: a tree of %d leaves has no NNI "
+                     "neighbours (3 or more are needed)", nl);
+  std::memset(nni_plan, 0, sizeof(int32_t) * TREX_PLAN_HEADER_INTS);
+  for (int b = 0; b < B; ++b) {
+    const char* why = nni_one_tree(children + (int64_t)b * n_all * 2, n_all,
+                                   nni_plan + TREX_PLAN_HEADER_INTS + b * nni_tree_ints(ni));
+    if (why)
+      return set_error(TREX_E_TOPOLOGY, "trex_nni_plan_build: tree %d is not a proper rooted "
+                       "binary tree: %s", b, why);
+  }
+  nni_plan[0] = kNniMagic;
+  nni_plan[1] = B;
+  nni_plan[2] = n_all;
+  nni_plan[3] = nl;
+  nni_plan[4] = ni;
+  return TREX_OK;
+}

@@ -1,0 +1,396 @@
+// NNI neighbour scores on the Sankoff DP table: the pre-order "outside" pass
+// and the O(Q^2) evaluation of every nearest-neighbour interchange per site
+// (DESIGN.md "NNI neighbour scoring").
+//
+// One tree, one site; (+) is min for tau = 0 and smin_tau for tau > 0;
+// C[parent][child]; D_x is node x's inside row (leaf: 0 at its code, 1e5
+// elsewhere; internal: the DP-table row):
+//   message       M_x[i] = (+)_j (C[i][j] + D_x[j])
+//   outside row   O_root = 0;  O_c[j] = (+)_i (C[i][j] + O_p[i] + M_s[i])
+//                 (p = c's parent, s = c's sibling)
+//   move (v, k)   swaps a_k of (a0, a1) = children[v] with v's sibling s
+//                 (u = v's parent):  D'_v = M_s + M_a(1-k),
+//                 site score = (+)_i (O_u[i] + M_ak[i] + M(D'_v)[i])
+// Both kernels give one 64-lane wave 64 consecutive sites of ONE tree (sites
+// on the lane axis), so the plan words (plan.cpp, NNI plan) and the cost
+// matrix are wave-uniform and read with scalar loads.  Q = 2, 3, 4 are
+// compile-time instantiations with every row in registers and one 8 / 12 /
+// 16-byte buffer access per row and lane; 4 < Q <= 20 runs the same code
+// padded to 20 states with wave-uniform guards on the live ones.  The softmin
+// is the stabilised form (row minimum subtracted).  Neighbour scores are
+// summed over a wave's sites in fp64 (fixed butterfly), the per-wave partials
+// over a tree's tiles in a fixed order by a second kernel: no float atomics,
+// bitwise reproducible.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+
+#include "sankoff_dev.h"
+#include "trex_common.h"
+
+namespace trex {
+
+namespace {
+
+constexpr int kNniPadQ = kSiteMaxQ;  // the generic path's padded alphabet
+
+struct NniArgs {
+  const int* plan;  // the NNI plan's per-tree regions (past the header)
+  const int8_t* leaves;
+  const float* cost;
+  const float* dp;
+  float* outside;
+  double* part;  // [B * tiles][ni - 1][2]
+  int B, L, nl, ni, Q, tiles;
+  float a, bcoef;
+};
+
+// DYN = false: Q == QP at compile time, the matrix in SGPRs.  DYN = true: QP
+// padded states, the live ones are j < Q (wave-uniform), matrix entries are
+// scalar loads at their use.
+template <int QP, bool DYN>
+struct CostM {
+  float c[DYN ? 1 : QP][DYN ? 1 : QP];
+  cptr<float> p;
+  int Q;
+  __device__ __forceinline__ void load(const float* cost, int q) {
+    p = as_const(cost);
+    Q = q;
+    if constexpr (!DYN) {
+#pragma unroll
+      for (int i = 0; i < QP; ++i)
+#pragma unroll
+        for (int j = 0; j < QP; ++j) c[i][j] = p[i * QP + j];
+    }
+  }
+  __device__ __forceinline__ bool live(int j) const { return !DYN || j < Q; }
+  __device__ __forceinline__ float at(int i, int j) const {
+    if constexpr (DYN) return p[i * Q + j];
+    else return c[i][j];
+  }
+};
+
+// (+) over the live entries of x
+template <int QP, bool DYN, bool SOFT>
+__device__ __forceinline__ float oplus(const CostM<QP, DYN>& cm, float a, float bcoef,
+                                       const float (&x)[QP]) {
+  float mn = INFINITY;
+#pragma unroll
+  for (int j = 0; j < QP; ++j)
+    if (cm.live(j)) mn = fminf(mn, x[j]);
+  if constexpr (!SOFT) return mn;
+  float acc = 0.0f;
+#pragma unroll
+  for (int j = 0; j < QP; ++j)
+    if (cm.live(j)) acc += fast_exp2((mn - x[j]) * a);
+  return fmaf(-bcoef, fast_log2(acc), mn);
+}
+
+// m[i] = (+)_j (C[i][j] + d[j]);  TRANS: m[j] = (+)_i (C[i][j] + d[i])
+template <int QP, bool DYN, bool SOFT, bool TRANS = false>
+__device__ __forceinline__ void message(const CostM<QP, DYN>& cm, float a, float bcoef,
+                                        const float (&d)[QP], float (&m)[QP]) {
+#pragma unroll
+  for (int i = 0; i < QP; ++i) {
+    m[i] = 0.0f;
+    if (cm.live(i)) {
+      float x[QP];
+#pragma unroll
+      for (int j = 0; j < QP; ++j) {
+        x[j] = 0.0f;
+        if (cm.live(j)) x[j] = (TRANS ? cm.at(j, i) : cm.at(i, j)) + d[j];
+      }
+      m[i] = oplus<QP, DYN, SOFT>(cm, a, bcoef, x);
+    }
+  }
+}
+
+// one tree's DP-layout table ([row][L][Q]): the lane's site of a row
+template <int QP, bool DYN>
+struct Rows {
+  rsrc_t r;
+  const float* base;
+  int L, Q, site;
+  __device__ __forceinline__ void init(const float* tree_base, int ni, int L_, int Q_, int site_) {
+    base = tree_base;
+    L = L_;
+    Q = Q_;
+    site = site_;
+    if constexpr (!DYN) r = make_rsrc(tree_base, (uint32_t)((size_t)ni * L_ * QP * 4));
+  }
+  __device__ __forceinline__ void get(int row, float (&d)[QP]) const {
+    if constexpr (!DYN) {
+      const int vo = site * QP * 4, so = row * L * QP * 4;
+      if constexpr (QP == 4) {
+        const u32x4 w = __builtin_amdgcn_raw_buffer_load_b128(r, vo, so, 0);
+        d[0] = __uint_as_float(w.x); d[1] = __uint_as_float(w.y);
+        d[2] = __uint_as_float(w.z); d[3] = __uint_as_float(w.w);
+      } else if constexpr (QP == 3) {
+        const u32x3 w = __builtin_amdgcn_raw_buffer_load_b96(r, vo, so, 0);
+        d[0] = __uint_as_float(w.x); d[1] = __uint_as_float(w.y); d[2] = __uint_as_float(w.z);
+      } else {
+        const u32x2 w = __builtin_amdgcn_raw_buffer_load_b64(r, vo, so, 0);
+        d[0] = __uint_as_float(w.x); d[1] = __uint_as_float(w.y);
+      }
+    } else {
+      const float* p = base + ((size_t)row * L + site) * Q;
+#pragma unroll
+      for (int j = 0; j < QP; ++j) d[j] = j < Q ? p[j] : 0.0f;
+    }
+  }
+  __device__ __forceinline__ void put(int row, const float (&d)[QP]) const {
+    if constexpr (!DYN) {
+      const int vo = site * QP * 4, so = row * L * QP * 4;
+      if constexpr (QP == 4) {
+        u32x4 w = {__float_as_uint(d[0]), __float_as_uint(d[1]), __float_as_uint(d[2]),
+                   __float_as_uint(d[3])};
+        __builtin_amdgcn_raw_buffer_store_b128(w, r, vo, so, 0);
+      } else if constexpr (QP == 3) {
+        u32x3 w = {__float_as_uint(d[0]), __float_as_uint(d[1]), __float_as_uint(d[2])};
+        __builtin_amdgcn_raw_buffer_store_b96(w, r, vo, so, 0);
+      } else {
+        u32x2 w = {__float_as_uint(d[0]), __float_as_uint(d[1])};
+        __builtin_amdgcn_raw_buffer_store_b64(w, r, vo, so, 0);
+      }
+    } else {
+      float* p = const_cast<float*>(base) + ((size_t)row * L + site) * Q;
+#pragma unroll
+      for (int j = 0; j < QP; ++j)
+        if (j < Q) p[j] = d[j];
+    }
+  }
+};
+
+// inside row of a plan descriptor (kind << 24 | index): a leaf's row from its
+// code, an internal node's from the DP table
+template <int QP, bool DYN>
+__device__ __forceinline__ void inside_row(int desc, const Rows<QP, DYN>& dp,
+                                           const int8_t* __restrict__ tree_leaves, int L, int site,
+                                           float (&d)[QP]) {
+  const int idx = desc & 0xFFFF;
+  if ((desc >> 24) == kKindLeaf) {
+    const int code = tree_leaves[(size_t)idx * L + site];
+#pragma unroll
+    for (int j = 0; j < QP; ++j) d[j] = code == j ? 0.0f : kSentinel;
+  } else {
+    dp.get(idx, d);
+  }
+}
+
+// Outside pass: a wave walks its tree's internal nodes in pre-order, reading
+// the parent's outside row it wrote earlier (same lane, same address) and the
+// sibling's inside row, writing the node's outside row.
+template <int QP, bool DYN, bool SOFT>
+__global__ __launch_bounds__(kWave) void nni_outside_kernel(const NniArgs A) {
+  const int lane = threadIdx.x;
+  const int b = blockIdx.x / A.tiles, tile = blockIdx.x % A.tiles;
+  const int l = tile * kWave + lane;
+  const bool on = l < A.L;
+  const int site = on ? l : A.L - 1;  // tail lanes recompute the last site, store nothing
+  CostM<QP, DYN> cm;
+  cm.load(A.cost, A.Q);
+  const size_t tree = (size_t)b * A.ni * A.L * A.Q;
+  Rows<QP, DYN> dp, out;
+  dp.init(A.dp + tree, A.ni, A.L, A.Q, site);
+  out.init(A.outside + tree, A.ni, A.L, A.Q, site);
+  const int8_t* lv = A.leaves + (size_t)b * A.nl * A.L;
+  const cptr<int> pre = as_const(A.plan) + (size_t)b * (8 * A.ni - 4);
+  for (int k = 0; k < A.ni; ++k) {
+    const I4 e = load_step(pre, k);
+    float oc[QP];
+    if (e.y < 0) {
+#pragma unroll
+      for (int j = 0; j < QP; ++j) oc[j] = 0.0f;
+    } else {
+      float t[QP], ds[QP], ms[QP];
+      out.get(e.y, t);
+      inside_row<QP, DYN>(e.z, dp, lv, A.L, site, ds);
+      message<QP, DYN, SOFT>(cm, A.a, A.bcoef, ds, ms);
+#pragma unroll
+      for (int i = 0; i < QP; ++i) t[i] += ms[i];
+      message<QP, DYN, SOFT, true>(cm, A.a, A.bcoef, t, oc);
+    }
+    if (on) out.put(e.x, oc);
+  }
+}
+
+// Neighbour scores: per non-root internal v both moves' site scores, summed
+// over the wave's sites in fp64; lane 0 writes the two partials.
+template <int QP, bool DYN, bool SOFT>
+__global__ __launch_bounds__(kWave) void nni_score_kernel(const NniArgs A) {
+  const int lane = threadIdx.x;
+  const int b = blockIdx.x / A.tiles, tile = blockIdx.x % A.tiles;
+  const int l = tile * kWave + lane;
+  const bool on = l < A.L;
+  const int site = on ? l : A.L - 1;
+  CostM<QP, DYN> cm;
+  cm.load(A.cost, A.Q);
+  const size_t tree = (size_t)b * A.ni * A.L * A.Q;
+  Rows<QP, DYN> dp, out;
+  dp.init(A.dp + tree, A.ni, A.L, A.Q, site);
+  out.init(A.outside + tree, A.ni, A.L, A.Q, site);
+  const int8_t* lv = A.leaves + (size_t)b * A.nl * A.L;
+  const cptr<int> mv = as_const(A.plan) + (size_t)b * (8 * A.ni - 4) + 4 * A.ni;
+  double* part = A.part + (size_t)blockIdx.x * (A.ni - 1) * 2;
+  for (int e = 0; e < A.ni - 1; ++e) {
+    const I4 m = load_step(mv, e);
+    float ou[QP], d[QP], m0[QP], m1[QP], ms[QP];
+    out.get(m.x, ou);
+    inside_row<QP, DYN>(m.y, dp, lv, A.L, site, d);
+    message<QP, DYN, SOFT>(cm, A.a, A.bcoef, d, m0);
+    inside_row<QP, DYN>(m.z, dp, lv, A.L, site, d);
+    message<QP, DYN, SOFT>(cm, A.a, A.bcoef, d, m1);
+    inside_row<QP, DYN>(m.w, dp, lv, A.L, site, d);
+    message<QP, DYN, SOFT>(cm, A.a, A.bcoef, d, ms);
+    float sc[2];
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      // v keeps a(1-k) and takes s; u keeps v and takes ak
+      float dv[QP], mdv[QP], x[QP];
+#pragma unroll
+      for (int j = 0; j < QP; ++j) dv[j] = ms[j] + (k == 0 ? m1[j] : m0[j]);
+      message<QP, DYN, SOFT>(cm, A.a, A.bcoef, dv, mdv);
+#pragma unroll
+      for (int i = 0; i < QP; ++i) x[i] = ou[i] + (k == 0 ? m0[i] : m1[i]) + mdv[i];
+      sc[k] = oplus<QP, DYN, SOFT>(cm, A.a, A.bcoef, x);
+    }
+    const double s0 = wave_sum_lane0(on ? (double)sc[0] : 0.0);
+    const double s1 = wave_sum_lane0(on ? (double)sc[1] : 0.0);
+    if (lane == 0) {
+      part[2 * e] = s0;
+      part[2 * e + 1] = s1;
+    }
+  }
+}
+
+// score[b][e][k] = the tiles' partials summed in tile order, rounded to fp32
+__global__ __launch_bounds__(256) void nni_reduce_kernel(const double* __restrict__ part, int B,
+                                                         int tiles, int moves,
+                                                         float* __restrict__ score) {
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= (int64_t)B * moves) return;
+  const int64_t b = t / moves, m = t % moves;
+  const double* p = part + b * tiles * moves + m;
+  double acc = 0.0;
+  for (int k = 0; k < tiles; ++k) acc += p[(int64_t)k * moves];
+  score[t] = (float)acc;
+}
+
+int nni_hip_check(const char* fn) {
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return set_error(TREX_E_HIP, "%s: %s", fn, hipGetErrorString(e));
+  return TREX_OK;
+}
+
+int nni_check_shape(const char* fn, int B, int L, int n_all, int Q, float tau) {
+  if (B <= 0 || L <= 0 || n_all < 3 || n_all > 65535 || n_all % 2 == 0 || Q < 2)
+    return set_error(TREX_E_ARG, "%s: bad shape B=%d L=%d n_all=%d Q=%d", fn, B, L, n_all, Q);
+  if (n_all < 5)
+    return set_error(TREX_E_TOPOLOGY, "%s: a tree of %d leaves has no NNI neighbours", fn,
+                     (n_all + 1) / 2);
+  if (Q > kSiteMaxQ)
+    return set_error(TREX_E_UNSUPPORTED, "%s: Q=%d > %d is not supported by the NNI kernels", fn,
+                     Q, kSiteMaxQ);
+  if (!nonneg_finite_f32(tau))
+    return set_error(TREX_E_ARG, "%s: tau must be finite and >= 0 (got %g)", fn, tau);
+  const int ni = n_all - (n_all + 1) / 2;
+  if ((int64_t)ni * L * Q * 4 > 0x7FFFFFF0LL)
+    return set_error(TREX_E_UNSUPPORTED, "%s: one tree's DP table exceeds 2 GiB", fn);
+  if ((int64_t)B * ((L + kWave - 1) / kWave) > 0x7FFFFFFF)
+    return set_error(TREX_E_ARG, "%s: grid too large", fn);
+  return TREX_OK;
+}
+
+void nni_fill(NniArgs& A, const int32_t* nni_plan, const int8_t* leaves, const float* cost, int B,
+              int L, int n_all, int Q, float tau, const float* dp, float* outside) {
+  A.plan = nni_plan + TREX_PLAN_HEADER_INTS;
+  A.leaves = leaves;
+  A.cost = cost;
+  A.dp = dp;
+  A.outside = outside;
+  A.part = nullptr;
+  A.B = B;
+  A.L = L;
+  A.nl = (n_all + 1) / 2;
+  A.ni = n_all - A.nl;
+  A.Q = Q;
+  A.tiles = (L + kWave - 1) / kWave;
+  if (tau > 0.0f) {
+    A.a = (float)(1.4426950408889634 / (double)tau);
+    A.bcoef = (float)((double)tau * 0.6931471805599453);
+  } else {
+    A.a = 0.0f;
+    A.bcoef = 0.0f;
+  }
+}
+
+template <bool SCORE, int QP, bool DYN>
+void nni_launch_q(bool soft, hipStream_t st, const NniArgs& A) {
+  const dim3 grid(A.B * A.tiles), block(kWave);
+  if constexpr (SCORE) {
+    if (soft) hipLaunchKernelGGL((nni_score_kernel<QP, DYN, true>), grid, block, 0, st, A);
+    else hipLaunchKernelGGL((nni_score_kernel<QP, DYN, false>), grid, block, 0, st, A);
+  } else {
+    if (soft) hipLaunchKernelGGL((nni_outside_kernel<QP, DYN, true>), grid, block, 0, st, A);
+    else hipLaunchKernelGGL((nni_outside_kernel<QP, DYN, false>), grid, block, 0, st, A);
+  }
+}
+
+template <bool SCORE>
+void nni_launch(bool soft, hipStream_t st, const NniArgs& A) {
+  switch (A.Q) {
+    case 2: nni_launch_q<SCORE, 2, false>(soft, st, A); break;
+    case 3: nni_launch_q<SCORE, 3, false>(soft, st, A); break;
+    case 4: nni_launch_q<SCORE, 4, false>(soft, st, A); break;
+    default: nni_launch_q<SCORE, kNniPadQ, true>(soft, st, A); break;
+  }
+}
+
+}  // namespace
+
+}  // namespace trex
+
+using namespace trex;
+
+extern "C" int trex_sankoff_outside(const int32_t* nni_plan, const int8_t* leaves,
+                                    const float* cost, int B, int L, int n_all, int Q, float tau,
+                                    const float* dp, float* outside, void* stream) {
+  const char* fn = "trex_sankoff_outside";
+  if (int e = nni_check_shape(fn, B, L, n_all, Q, tau)) return e;
+  if (!nni_plan || !leaves || !cost || !dp || !outside)
+    return set_error(TREX_E_ARG, "%s: null pointer argument", fn);
+  NniArgs A;
+  nni_fill(A, nni_plan, leaves, cost, B, L, n_all, Q, tau, dp, outside);
+  nni_launch<false>(tau > 0.0f, (hipStream_t)stream, A);
+  return nni_hip_check(fn);
+}
+
+extern "C" int64_t trex_nni_workspace_bytes(int B, int L, int n_all, int Q) {
+  if (B <= 0 || L <= 0 || n_all < 5 || n_all % 2 == 0 || Q < 2 || Q > kSiteMaxQ) return 0;
+  const int64_t ni = n_all - (n_all + 1) / 2;
+  return (int64_t)B * ((L + kWave - 1) / kWave) * (ni - 1) * 2 * 8 + 256;
+}
+
+extern "C" int trex_sankoff_nni(const int32_t* nni_plan, const int8_t* leaves, const float* cost,
+                                int B, int L, int n_all, int Q, float tau, const float* dp,
+                                const float* outside, float* nni_score, void* workspace,
+                                int64_t workspace_bytes, void* stream) {
+  const char* fn = "trex_sankoff_nni";
+  if (int e = nni_check_shape(fn, B, L, n_all, Q, tau)) return e;
+  if (!nni_plan || !leaves || !cost || !dp || !outside || !nni_score || !workspace)
+    return set_error(TREX_E_ARG, "%s: null pointer argument", fn);
+  if (workspace_bytes < trex_nni_workspace_bytes(B, L, n_all, Q))
+    return set_error(TREX_E_ARG, "%s: workspace too small", fn);
+  NniArgs A;
+  nni_fill(A, nni_plan, leaves, cost, B, L, n_all, Q, tau, dp, const_cast<float*>(outside));
+  A.part = static_cast<double*>(workspace);
+  hipStream_t st = (hipStream_t)stream;
+  nni_launch<true>(tau > 0.0f, st, A);
+  if (int e = nni_hip_check(fn)) return e;
+  const int moves = (A.ni - 1) * 2;
+  const int64_t n = (int64_t)B * moves;
+  hipLaunchKernelGGL(nni_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
+                     A.part, B, A.tiles, moves, nni_score);
+  return nni_hip_check(fn);
+}

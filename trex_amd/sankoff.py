@@ -227,6 +227,54 @@ class SankoffEngine:
             self.Q, ptr(an), stream_handle(self.device)))
         return an
 
+    # -- NNI neighbour scores (sankoff_nni.hip) ------------------------------
+    def _check_table(self, t, what):
+        torch = _torch()
+        if (t is None or t.dtype != torch.float32 or tuple(t.shape) != self.dp_shape
+                or not t.is_contiguous() or t.device != self.device):
+            raise ValueError(f"{what} must be a contiguous float32 {self.dp_shape} tensor on the "
+                             "engine's device")
+
+    def outside(self, leaves, cost, tau: float, dp):
+        """Outside table (B, n_int, L, Q) of ``dp`` (a forward's table at the
+        same tau): O_root = 0, O_c[j] = (+)_i (C[i][j] + O_p[i] + M_s[i])."""
+        torch = _torch()
+        self._check_inputs(leaves, cost)
+        self._check_table(dp, "dp")
+        p = self.plan
+        out = torch.empty(self.dp_shape, dtype=torch.float32, device=self.device)
+        check(lib().trex_sankoff_outside(
+            ptr(p.nni_device(self.device)), ptr(leaves), ptr(cost), p.B, self.L, p.n_all, self.Q,
+            float(tau), ptr(dp), ptr(out), stream_handle(self.device)))
+        return out
+
+    def nni_scores(self, leaves, cost, tau: float = 0.0, *, dp=None, outside=None):
+        """Tree scores of all NNI neighbours, float32 (B, n_int - 1, 2): entry
+        [b, v - n_leaves, k] is tree b after ``apply_nni(children[b], v, k)``
+        (plain score: no hard_root).  Runs the forward and / or the outside
+        pass when ``dp`` / ``outside`` are not given."""
+        torch = _torch()
+        self._check_inputs(leaves, cost)
+        p = self.plan
+        if dp is None:
+            if outside is not None:
+                raise ValueError("outside without the dp table it was computed from")
+            dp = self.forward(leaves, cost, tau).dp
+        self._check_table(dp, "dp")
+        if outside is None:
+            outside = self.outside(leaves, cost, tau, dp)
+        self._check_table(outside, "outside")
+        nbytes = lib().trex_nni_workspace_bytes(p.B, self.L, p.n_all, self.Q)
+        ws = getattr(self, "_nni_ws", None)
+        if ws is None or ws.numel() < max(nbytes, 1):
+            ws = self._nni_ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=self.device)
+        score = torch.empty((p.B, p.n_int - 1, 2), dtype=torch.float32, device=self.device)
+        check(lib().trex_sankoff_nni(
+            ptr(p.nni_device(self.device)), ptr(leaves), ptr(cost), p.B, self.L, p.n_all, self.Q,
+            float(tau), ptr(dp), ptr(outside), ptr(score), ptr(ws), ws.numel(),
+            stream_handle(self.device)))
+        return score
+
     def value_and_grad(self, leaves, cost, tau: float = 0.0, d_tree_score=None,
                        hard_root=False):
         """(tree_score (B,), d_cost (Q, Q)) -- fused fwd + adjoint launch."""

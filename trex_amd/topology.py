@@ -87,6 +87,60 @@ def adjacency_from_children(children: np.ndarray) -> np.ndarray:
     return adj
 
 
+def apply_nni(children, v: int, k: int) -> np.ndarray:
+    """Child lists (n_all, 2) of the NNI neighbour (v, k) of one tree.
+
+    ``v`` is an internal node other than the root, u its parent, s its
+    sibling and (a0, a1) = ``children[v]`` in stored order; the move swaps
+    a_k with s, so v gets {s, a_(1-k)} and u gets {a_k, v} (the move of
+    ``SankoffEngine.nni_scores``' entry ``[v - n_leaves, k]``).  The result
+    is valid under trex's numbering: leaf ids are unchanged, internal nodes
+    are renumbered in post-order by a DFS from the root that visits children
+    in ascending id order, so every child id is below its parent's and the
+    root is n_all - 1; each pair is stored ascending.
+    """
+    ch = np.asarray(children)
+    if ch.ndim != 2 or ch.shape[1] != 2:
+        raise ValueError(f"children must be (n_all, 2), got {ch.shape}")
+    n_all = ch.shape[0]
+    nl = (n_all + 1) // 2
+    if not (nl <= v < n_all - 1) or k not in (0, 1):
+        raise ValueError(f"move ({v}, {k}): v must be internal and not the root, k 0 or 1")
+    kids = {node: [int(ch[node, 0]), int(ch[node, 1])] for node in range(nl, n_all)}
+    parents = [u for u, pair in kids.items() if v in pair]
+    if len(parents) != 1:
+        raise ValueError(f"node {v} does not have exactly one parent")
+    u = parents[0]
+    s = kids[u][0] if kids[u][1] == v else kids[u][1]
+    a = kids[v]
+    kids[v] = [s, a[1 - k]]
+    kids[u] = [a[k], v]
+    # post-order renumbering, children in ascending id order
+    new_id = {c: c for c in range(nl)}
+    out = np.full((n_all, 2), -1, dtype=np.int32)
+    nxt = nl
+    stack = [(n_all - 1, False)]
+    while stack:
+        node, done = stack.pop()
+        if node < nl:
+            continue
+        if not done:
+            if len(stack) > 2 * n_all:
+                raise ValueError("children do not describe a tree")
+            stack.append((node, True))
+            for c in sorted(kids[node], reverse=True):
+                stack.append((c, False))
+            continue
+        if nxt >= n_all:
+            raise ValueError("children do not describe a tree")
+        new_id[node] = nxt
+        out[nxt] = sorted(new_id[c] for c in kids[node])
+        nxt += 1
+    if nxt != n_all:
+        raise ValueError("children do not describe a tree")
+    return out
+
+
 class TreePlan:
     """A batch of topologies compiled by the host planner (trex_plan_build)."""
 
@@ -117,6 +171,49 @@ class TreePlan:
         self.n_dag_nodes = int(info[2])
         self.n_unreached = int(info[3])
         self._dev = {}
+        self._nni_host = None
+        self._nni_dev = {}
+
+    # -- NNI plan (trex_nni_plan_build), built on first use ------------------
+    @property
+    def nni_host(self) -> np.ndarray:
+        """The NNI plan (include/trex_hip.h) as int32; TrexError
+        (TREX_E_TOPOLOGY) when a tree of the batch is not a proper rooted
+        binary tree of at least 3 leaves."""
+        if self._nni_host is None:
+            L = lib()
+            n = L.trex_nni_plan_ints(self.B, self.n_all)
+            if n <= 0:
+                raise ValueError(f"bad NNI plan shape B={self.B} n_all={self.n_all}")
+            buf = np.zeros(n, dtype=np.int32)
+            check(L.trex_nni_plan_build(self.children.ctypes.data, self.B, self.n_all,
+                                        buf.ctypes.data))
+            self._nni_host = buf
+        return self._nni_host
+
+    def nni_device(self, device):
+        """The NNI plan as an int32 device tensor (cached per device)."""
+        import torch
+
+        key = str(device)
+        if key not in self._nni_dev:
+            self._nni_dev[key] = torch.from_numpy(self.nni_host).to(device)
+        return self._nni_dev[key]
+
+    @property
+    def nni_table(self) -> np.ndarray:
+        """int32 (B, n_int - 1, 4): node ids (u, a0, a1, s) of v = n_leaves + e
+        -- v's parent, its two children in stored order and its sibling --
+        decoded from the NNI plan.  Move (v, k) swaps a_k with s."""
+        ni = self.n_int
+        per = 8 * ni - 4
+        body = self.nni_host[TREX_PLAN_HEADER_INTS:].reshape(self.B, per)
+        mv = body[:, 4 * ni:].reshape(self.B, ni - 1, 4)
+        out = np.empty_like(mv)
+        out[:, :, 0] = mv[:, :, 0] + self.n_leaves
+        d = mv[:, :, 1:]
+        out[:, :, 1:] = np.where((d >> 24) == 1, d & 0xFFFF, (d & 0xFFFF) + self.n_leaves)
+        return out
 
     @classmethod
     def from_adjacency(cls, adj) -> "TreePlan":
