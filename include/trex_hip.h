@@ -579,6 +579,43 @@ int trex_sankoff_nni(const int32_t* nni_plan, const int8_t* leaves, const float*
                      int L, int n_all, int Q, float tau, const float* dp, const float* outside,
                      float* nni_score, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Attachment scores: the plain score of every tree of the batch after a
+ * given subtree is attached on each of its n_all edges (the n_all - 1 edges
+ * above the nodes below the root, and a new root above the old one), from
+ * the same dp and outside tables.  D_new = the subtree's inside row (a leaf
+ * code: 0 at the code, 1e5 elsewhere, all 1e5 for code -1), M_new its
+ * message.  Attaching on the edge above node x makes a node w with children
+ * x and the subtree:
+ *   x below p, sibling s:  D_w = M_x + M_new,
+ *                          site score = (+)_i (O_p[i] + M_s[i] + M(D_w)[i])
+ *   x the root:            site score = (+)_k (M_root[k] + M_new[k])
+ * Stepwise addition attaches a leaf; the regraft half of an SPR move attaches
+ * the root DP row of the pruned subtree.
+ *
+ * trex_attach_plan_build [host]: accepts what trex_nni_plan_build accepts,
+ *   same error codes.  attach_plan: int32 buffer of trex_attach_plan_ints(B,
+ *   n_all) ints (copy it to the device unchanged): header
+ *   [TREX_PLAN_HEADER_INTS] (magic, B, n_all, n_leaves, n_int), then per tree
+ *   [n_int][4] = {internal row p, descriptor of child 0, descriptor of
+ *   child 1, 1 if p is the root else 0}: rows ascending, children in stored
+ *   order, descriptors as in the NNI plan.
+ * trex_sankoff_attach: exactly one of sub_codes (int8 [B][L]) and sub_rows
+ *   (fp32 [B][L][Q]) is non-null, else TREX_E_ARG.  attach_score fp32
+ *   [B][n_all]: entry [b][x] = the tree score after attaching on the edge
+ *   above node id x; x = n_all - 1 is the new root.  Shapes, the Q <= 20
+ *   limit, the fp64 fixed-order site sums and the workspace rules are those
+ *   of trex_sankoff_nni (workspace >= trex_attach_workspace_bytes bytes).
+ * ---------------------------------------------------------------------- */
+int64_t trex_attach_plan_ints(int B, int n_all);
+int trex_attach_plan_build(const int32_t* children, int B, int n_all, int32_t* attach_plan);
+int64_t trex_attach_workspace_bytes(int B, int L, int n_all, int Q);
+int trex_sankoff_attach(const int32_t* attach_plan, const int8_t* leaves, const float* cost,
+                        int B, int L, int n_all, int Q, float tau, const float* dp,
+                        const float* outside, const int8_t* sub_codes, const float* sub_rows,
+                        float* attach_score, void* workspace, int64_t workspace_bytes,
+                        void* stream);
+
 /* ========================================================================
  * Synthetic data on the device: trex's
  * generate_groundtruth (src/trex/ground_truth.py:112-197, mutate :20-52) and

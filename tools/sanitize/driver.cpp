@@ -4,7 +4,8 @@
 //     batches) on random, quirky (-1 fills, forward references, DAGs,
 //     orphans), cyclic and malformed child lists, writing into buffers sized
 //     exactly by trex_plan_ints / trex_ragged_plan_ints, and the NNI planner
-//     (trex_nni_plan_build) on the same trees, its accepted plans range-checked;
+//     (trex_nni_plan_build) and the attach planner (trex_attach_plan_build) on
+//     the same trees, their accepted plans range-checked;
 //   * oracle/cpu_port.c -- the OpenMP C restatement (the CPU baseline and a
 //     test checker) on random trees, Q = 2..20, hard and softmin, with and
 //     without the DP table output.
@@ -151,6 +152,57 @@ int check_nni() {
   return 0;
 }
 
+// the attach planner accepts the same trees as the NNI planner; an accepted
+// plan lists every node below the root once, as a child of an ascending row
+int check_attach() {
+  int built = 0, refused = 0;
+  for (int it = 0; it < 400; ++it) {
+    const int nl = rnd(2, 128);
+    const int n_all = 2 * nl - 1;
+    const int ni = n_all - nl;
+    const int B = rnd(1, 6);
+    std::vector<int32_t> ch((size_t)B * n_all * 2);
+    bool clean = true;
+    for (int b = 0; b < B; ++b) {
+      random_tree(nl, ch.data() + (size_t)b * n_all * 2);
+      if (it % 2) {
+        const int mode = rnd(0, 4);
+        perturb(nl, ch.data() + (size_t)b * n_all * 2, mode);
+        clean = clean && mode == 4;
+      }
+    }
+    const int64_t n = trex_attach_plan_ints(B, n_all);
+    if (n != TREX_PLAN_HEADER_INTS + (int64_t)B * ni * 4) return 12;
+    std::vector<int32_t> plan((size_t)n), nni((size_t)trex_nni_plan_ints(B, n_all));
+    const int rc = trex_attach_plan_build(ch.data(), B, n_all, plan.data());
+    if (rc != 0 && rc != TREX_E_TOPOLOGY && rc != TREX_E_ARG) return 13;
+    if (rc != trex_nni_plan_build(ch.data(), B, n_all, nni.data())) return 14;  // same rule
+    if (clean && nl >= 3 && rc != 0) return 15;
+    if (nl < 3 && rc == 0) return 16;
+    if (rc != 0) {
+      ++refused;
+      continue;
+    }
+    ++built;
+    for (int b = 0; b < B; ++b) {
+      const int32_t* r = plan.data() + TREX_PLAN_HEADER_INTS + (size_t)b * ni * 4;
+      std::vector<int> seen(n_all, 0);
+      for (int k = 0; k < ni; ++k) {
+        if (r[4 * k] != k || r[4 * k + 3] != (k == ni - 1 ? 1 : 0)) return 17;
+        for (int c = 1; c <= 2; ++c) {
+          const int kind = r[4 * k + c] >> 24, idx = r[4 * k + c] & 0xFFFF;
+          if (!((kind == 1 && idx < nl) || (kind == 2 && idx < k))) return 18;
+          ++seen[kind == 1 ? idx : nl + idx];
+        }
+      }
+      for (int x = 0; x < n_all - 1; ++x)
+        if (seen[x] != 1) return 19;
+    }
+  }
+  std::printf("attach plans: %d built, %d refused\n", built, refused);
+  return 0;
+}
+
 int check_ragged() {
   for (int it = 0; it < 200; ++it) {
     const int B = rnd(1, 8);
@@ -214,6 +266,7 @@ int main() {
   if (int e = check_ragged()) return e;
   if (int e = check_cpu_port()) return e;
   if (int e = check_nni()) return e;
+  if (int e = check_attach()) return e;
   std::printf("sanitize ok\n");
   return 0;
 }

@@ -16,13 +16,22 @@ from .sankoff import (  # noqa: F401
     vectorized_dp,
     vmapped_backtrack,
 )
-from .search import HillClimbResult, nni_hill_climb  # noqa: F401
+from .search import (  # noqa: F401
+    HillClimbResult,
+    SearchResult,
+    StepwiseResult,
+    nni_hill_climb,
+    parsimony_search,
+    stepwise_addition,
+)
 from .topology import (  # noqa: F401
     TreePlan,
     apply_nni,
     children_from_adjacency,
     create_balanced_binary_tree,
+    insert_leaf,
     random_topologies,
+    relabel_leaves,
 )
 
 __all__ = [
@@ -30,5 +39,6 @@ __all__ = [
     "vectorized_dp", "backtrack_sankoff_jit", "vmapped_backtrack",
     "sankoff_value_and_grad", "TreePlan", "children_from_adjacency",
     "create_balanced_binary_tree", "random_topologies", "apply_nni", "nni_hill_climb",
-    "HillClimbResult",
+    "HillClimbResult", "insert_leaf", "relabel_leaves", "stepwise_addition", "StepwiseResult",
+    "parsimony_search", "SearchResult",
 ]

@@ -52,6 +52,12 @@ SIGNATURES = {
     "trex_nni_workspace_bytes": (_c_i64, [_c_i, _c_i, _c_i, _c_i]),
     "trex_sankoff_nni": (_c_i, [_p, _p, _p, _c_i, _c_i, _c_i, _c_i, _c_f, _p, _p, _p, _p, _c_i64,
                                 _p]),
+    # attachment scores on every edge (stepwise addition, SPR regraft)
+    "trex_attach_plan_ints": (_c_i64, [_c_i, _c_i]),
+    "trex_attach_plan_build": (_c_i, [_p, _c_i, _c_i, _p]),
+    "trex_attach_workspace_bytes": (_c_i64, [_c_i, _c_i, _c_i, _c_i]),
+    "trex_sankoff_attach": (_c_i, [_p, _p, _p, _c_i, _c_i, _c_i, _c_i, _c_f, _p, _p, _p, _p, _p,
+                                   _p, _c_i64, _p]),
     # multi-GPU exchange (RCCL, dlopen'ed on first use)
     "trex_comm_unique_id_bytes": (_c_i, []),
     "trex_comm_get_unique_id": (_c_i, [_p]),

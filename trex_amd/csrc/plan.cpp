@@ -636,11 +636,11 @@ namespace {
 constexpr int32_t kNniMagic = 0x54524E4E;  // 'TRNN'
 inline int64_t nni_tree_ints(int ni) { return 8LL * ni - 4; }
 
-// nullptr when the tree is a proper rooted binary tree, else what is wrong
-const char* nni_one_tree(const int32_t* ch, int n_all, int32_t* region) {
+// nullptr when the tree is a proper rooted binary tree (parent[] is then
+// filled), else what is wrong
+const char* proper_tree_parents(const int32_t* ch, int n_all, std::vector<int>& parent) {
   const int nl = (n_all + 1) / 2;
-  const int ni = n_all - nl;
-  std::vector<int> parent(n_all, -1);
+  parent.assign(n_all, -1);
   for (int node = nl; node < n_all; ++node) {
     const int c0 = ch[2 * node], c1 = ch[2 * node + 1];
     if (c0 < 0 || c1 < 0) return "a child is missing (-1 fill)";
@@ -653,6 +653,14 @@ const char* nni_one_tree(const int32_t* ch, int n_all, int32_t* region) {
   // 2 ni child slots, all distinct, over the n_all - 1 = 2 ni nodes below the
   // root: every one of them has exactly one parent, of a higher id, so every
   // path leads up to the root n_all - 1
+  return nullptr;
+}
+
+const char* nni_one_tree(const int32_t* ch, int n_all, int32_t* region) {
+  const int nl = (n_all + 1) / 2;
+  const int ni = n_all - nl;
+  std::vector<int> parent;
+  if (const char* why = proper_tree_parents(ch, n_all, parent)) return why;
   auto desc = [&](int c) -> int32_t {
     return c < nl ? (c | (kKindLeaf << 24)) : ((c - nl) | (kKindInt << 24));
   };
@@ -717,5 +725,61 @@ extern "C" int trex_nni_plan_build(const int32_t* children, int B, int n_all, in
   nni_plan[2] = n_all;
   nni_plan[3] = nl;
   nni_plan[4] = ni;
+  return TREX_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Attach plan (sankoff_nni.hip, attach_score_kernel): the edges of every tree
+// grouped by their upper node.  Layout (ints): header [16] | per tree
+// [ni][4]: entry r = {internal row r, descriptor of child 0, descriptor of
+// child 1, 1 if r is the root else 0}, rows ascending, children in stored
+// order, descriptors as in the NNI plan.  The same trees are accepted as by
+// trex_nni_plan_build.
+// ---------------------------------------------------------------------------
+namespace trex {
+namespace {
+constexpr int32_t kAttachMagic = 0x54524154;  // 'TRAT'
+}  // namespace
+}  // namespace trex
+
+extern "C" int64_t trex_attach_plan_ints(int B, int n_all) {
+  if (B <= 0 || n_all < 3 || n_all > 65535) return 0;
+  const int ni = n_all - (n_all + 1) / 2;
+  return TREX_PLAN_HEADER_INTS + (int64_t)B * ni * 4;
+}
+
+extern "C" int trex_attach_plan_build(const int32_t* children, int B, int n_all,
+                                      int32_t* attach_plan) {
+  using namespace trex;
+  if (!children || !attach_plan || B <= 0 || n_all < 3 || n_all > 65535 || n_all % 2 == 0)
+    return set_error(TREX_E_ARG, "trex_attach_plan_build: bad arguments (B=%d n_all=%d)", B,
+                     n_all);
+  const int nl = (n_all + 1) / 2;
+  const int ni = n_all - nl;
+  if (nl < 3)
+    return set_error(TREX_E_TOPOLOGY, "trex_attach_plan_build: a tree of %d leaves is not "
+                     "supported (3 or more are needed)", nl);
+  std::memset(attach_plan, 0, sizeof(int32_t) * TREX_PLAN_HEADER_INTS);
+  std::vector<int> parent;
+  for (int b = 0; b < B; ++b) {
+    const int32_t* ch = children + (int64_t)b * n_all * 2;
+    if (const char* why = proper_tree_parents(ch, n_all, parent))
+      return set_error(TREX_E_TOPOLOGY, "trex_attach_plan_build: tree %d is not a proper rooted "
+                       "binary tree: %s", b, why);
+    int32_t* e = attach_plan + TREX_PLAN_HEADER_INTS + (int64_t)b * ni * 4;
+    for (int r = 0; r < ni; ++r) {
+      e[4 * r] = r;
+      for (int k = 0; k < 2; ++k) {
+        const int c = ch[2 * (nl + r) + k];
+        e[4 * r + 1 + k] = c < nl ? (c | (kKindLeaf << 24)) : ((c - nl) | (kKindInt << 24));
+      }
+      e[4 * r + 3] = r == ni - 1 ? 1 : 0;
+    }
+  }
+  attach_plan[0] = kAttachMagic;
+  attach_plan[1] = B;
+  attach_plan[2] = n_all;
+  attach_plan[3] = nl;
+  attach_plan[4] = ni;
   return TREX_OK;
 }

@@ -20,7 +20,9 @@
 // is the stabilised form (row minimum subtracted).  Neighbour scores are
 // summed over a wave's sites in fp64 (fixed butterfly), the per-wave partials
 // over a tree's tiles in a fixed order by a second kernel: no float atomics,
-// bitwise reproducible.
+// bitwise reproducible.  The attachment scores further down (a new leaf or a
+// subtree's row on every edge of a tree; DESIGN.md "Attachment scores") read
+// the same two tables with the same helpers.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -347,6 +349,112 @@ void nni_launch(bool soft, hipStream_t st, const NniArgs& A) {
   }
 }
 
+// ---- attachment scores (DESIGN.md "Attachment scores") -------------------
+// Attaching a subtree with inside row D_new (message M_new) on the edge above
+// node x makes a new node w with children x and the subtree:
+//   x below p, sibling s:  D_w = M_x + M_new,
+//                          site score = (+)_i (O_p[i] + M_s[i] + M(D_w)[i])
+//   x the root:            site score = (+)_k (M_root[k] + M_new[k])
+struct AttachArgs {
+  NniArgs n;  // n.plan: the attach plan's per-tree regions; n.part: [B * tiles][n_all]
+  const int8_t* sub_codes;  // [B][L], or
+  const float* sub_rows;    // [B][L][Q]
+};
+
+__device__ __forceinline__ int desc_node(int desc, int nl) {
+  return (desc >> 24) == kKindLeaf ? (desc & 0xFFFF) : nl + (desc & 0xFFFF);
+}
+
+// A wave walks its tree's internal rows p: both child edges of p from O_p and
+// the children's messages, on the root row also the new-root entry; site sums
+// in fp64, lane 0 writes the partials at the edges' lower node ids.
+template <int QP, bool DYN, bool SOFT>
+__global__ __launch_bounds__(kWave) void attach_score_kernel(const AttachArgs AA) {
+  const NniArgs& A = AA.n;
+  const int lane = threadIdx.x;
+  const int b = blockIdx.x / A.tiles, tile = blockIdx.x % A.tiles;
+  const int l = tile * kWave + lane;
+  const bool on = l < A.L;
+  const int site = on ? l : A.L - 1;
+  CostM<QP, DYN> cm;
+  cm.load(A.cost, A.Q);
+  const size_t tree = (size_t)b * A.ni * A.L * A.Q;
+  Rows<QP, DYN> dp, out;
+  dp.init(A.dp + tree, A.ni, A.L, A.Q, site);
+  out.init(A.outside + tree, A.ni, A.L, A.Q, site);
+  const int8_t* lv = A.leaves + (size_t)b * A.nl * A.L;
+  const cptr<int> pl = as_const(A.plan) + (size_t)b * 4 * A.ni;
+  const int n_all = A.nl + A.ni;
+  double* part = A.part + (size_t)blockIdx.x * n_all;
+  float mn[QP];
+  {
+    float dn[QP];
+    if (AA.sub_codes) {
+      const int code = AA.sub_codes[(size_t)b * A.L + site];
+#pragma unroll
+      for (int j = 0; j < QP; ++j) dn[j] = code == j ? 0.0f : kSentinel;
+    } else {
+      Rows<QP, DYN> sub;
+      sub.init(AA.sub_rows + (size_t)b * A.L * A.Q, 1, A.L, A.Q, site);
+      sub.get(0, dn);
+    }
+    message<QP, DYN, SOFT>(cm, A.a, A.bcoef, dn, mn);
+  }
+  for (int r = 0; r < A.ni; ++r) {
+    const I4 e = load_step(pl, r);
+    float op[QP], d[QP], m0[QP], m1[QP];
+    out.get(e.x, op);
+    inside_row<QP, DYN>(e.y, dp, lv, A.L, site, d);
+    message<QP, DYN, SOFT>(cm, A.a, A.bcoef, d, m0);
+    inside_row<QP, DYN>(e.z, dp, lv, A.L, site, d);
+    message<QP, DYN, SOFT>(cm, A.a, A.bcoef, d, m1);
+    float sc[2];
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      // the edge above child k: w takes child k and the subtree, p keeps the other child
+      float dw[QP], mdw[QP], x[QP];
+#pragma unroll
+      for (int j = 0; j < QP; ++j) dw[j] = (k == 0 ? m0[j] : m1[j]) + mn[j];
+      message<QP, DYN, SOFT>(cm, A.a, A.bcoef, dw, mdw);
+#pragma unroll
+      for (int i = 0; i < QP; ++i) x[i] = op[i] + (k == 0 ? m1[i] : m0[i]) + mdw[i];
+      sc[k] = oplus<QP, DYN, SOFT>(cm, A.a, A.bcoef, x);
+    }
+    const double s0 = wave_sum_lane0(on ? (double)sc[0] : 0.0);
+    const double s1 = wave_sum_lane0(on ? (double)sc[1] : 0.0);
+    if (lane == 0) {
+      part[desc_node(e.y, A.nl)] = s0;
+      part[desc_node(e.z, A.nl)] = s1;
+    }
+    if (e.w) {  // a new root above the old one
+      float x[QP];
+      dp.get(e.x, d);
+      message<QP, DYN, SOFT>(cm, A.a, A.bcoef, d, m0);
+#pragma unroll
+      for (int i = 0; i < QP; ++i) x[i] = m0[i] + mn[i];
+      const float sr = oplus<QP, DYN, SOFT>(cm, A.a, A.bcoef, x);
+      const double s2 = wave_sum_lane0(on ? (double)sr : 0.0);
+      if (lane == 0) part[A.nl + e.x] = s2;
+    }
+  }
+}
+
+template <int QP, bool DYN>
+void attach_launch_q(bool soft, hipStream_t st, const AttachArgs& A) {
+  const dim3 grid(A.n.B * A.n.tiles), block(kWave);
+  if (soft) hipLaunchKernelGGL((attach_score_kernel<QP, DYN, true>), grid, block, 0, st, A);
+  else hipLaunchKernelGGL((attach_score_kernel<QP, DYN, false>), grid, block, 0, st, A);
+}
+
+void attach_launch(bool soft, hipStream_t st, const AttachArgs& A) {
+  switch (A.n.Q) {
+    case 2: attach_launch_q<2, false>(soft, st, A); break;
+    case 3: attach_launch_q<3, false>(soft, st, A); break;
+    case 4: attach_launch_q<4, false>(soft, st, A); break;
+    default: attach_launch_q<kNniPadQ, true>(soft, st, A); break;
+  }
+}
+
 }  // namespace
 
 }  // namespace trex
@@ -392,5 +500,37 @@ extern "C" int trex_sankoff_nni(const int32_t* nni_plan, const int8_t* leaves, c
   const int64_t n = (int64_t)B * moves;
   hipLaunchKernelGGL(nni_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
                      A.part, B, A.tiles, moves, nni_score);
+  return nni_hip_check(fn);
+}
+
+extern "C" int64_t trex_attach_workspace_bytes(int B, int L, int n_all, int Q) {
+  if (B <= 0 || L <= 0 || n_all < 5 || n_all % 2 == 0 || Q < 2 || Q > kSiteMaxQ) return 0;
+  return (int64_t)B * ((L + kWave - 1) / kWave) * n_all * 8 + 256;
+}
+
+extern "C" int trex_sankoff_attach(const int32_t* attach_plan, const int8_t* leaves,
+                                   const float* cost, int B, int L, int n_all, int Q, float tau,
+                                   const float* dp, const float* outside, const int8_t* sub_codes,
+                                   const float* sub_rows, float* attach_score, void* workspace,
+                                   int64_t workspace_bytes, void* stream) {
+  const char* fn = "trex_sankoff_attach";
+  if (int e = nni_check_shape(fn, B, L, n_all, Q, tau)) return e;
+  if (!attach_plan || !leaves || !cost || !dp || !outside || !attach_score || !workspace)
+    return set_error(TREX_E_ARG, "%s: null pointer argument", fn);
+  if ((sub_codes == nullptr) == (sub_rows == nullptr))
+    return set_error(TREX_E_ARG, "%s: exactly one of sub_codes and sub_rows must be given", fn);
+  if (workspace_bytes < trex_attach_workspace_bytes(B, L, n_all, Q))
+    return set_error(TREX_E_ARG, "%s: workspace too small", fn);
+  AttachArgs A;
+  nni_fill(A.n, attach_plan, leaves, cost, B, L, n_all, Q, tau, dp, const_cast<float*>(outside));
+  A.n.part = static_cast<double*>(workspace);
+  A.sub_codes = sub_codes;
+  A.sub_rows = sub_rows;
+  hipStream_t st = (hipStream_t)stream;
+  attach_launch(tau > 0.0f, st, A);
+  if (int e = nni_hip_check(fn)) return e;
+  const int64_t n = (int64_t)B * n_all;
+  hipLaunchKernelGGL(nni_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
+                     A.n.part, B, A.n.tiles, n_all, attach_score);
   return nni_hip_check(fn);
 }

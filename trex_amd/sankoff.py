@@ -275,6 +275,46 @@ class SankoffEngine:
             stream_handle(self.device)))
         return score
 
+    def attach_scores(self, leaves, cost, tau: float = 0.0, *, new_leaf=None, sub_rows=None,
+                      dp=None, outside=None):
+        """Tree scores after attaching a subtree on every edge, float32
+        (B, n_all): entry [b, x] is tree b with the subtree on the edge above
+        node x (``insert_leaf(children[b], x)`` for a leaf; x = n_all - 1 is a
+        new root; plain score).  The subtree is ``new_leaf``, int8 (B, L) leaf
+        codes, or ``sub_rows``, float32 (B, L, Q) inside rows (a subtree's
+        root DP row).  Runs the forward and / or the outside pass when ``dp``
+        / ``outside`` are not given."""
+        torch = _torch()
+        self._check_inputs(leaves, cost)
+        p = self.plan
+        if (new_leaf is None) == (sub_rows is None):
+            raise ValueError("give exactly one of new_leaf and sub_rows")
+        sub, dtype, shape = ((new_leaf, torch.int8, (p.B, self.L)) if sub_rows is None else
+                             (sub_rows, torch.float32, (p.B, self.L, self.Q)))
+        if (not hasattr(sub, "dtype") or sub.dtype != dtype or tuple(sub.shape) != shape
+                or not sub.is_contiguous() or sub.device != self.device):
+            raise ValueError(f"{'new_leaf' if sub_rows is None else 'sub_rows'} must be a "
+                             f"contiguous {dtype} {shape} tensor on the engine's device")
+        if dp is None:
+            if outside is not None:
+                raise ValueError("outside without the dp table it was computed from")
+            dp = self.forward(leaves, cost, tau).dp
+        self._check_table(dp, "dp")
+        if outside is None:
+            outside = self.outside(leaves, cost, tau, dp)
+        self._check_table(outside, "outside")
+        nbytes = lib().trex_attach_workspace_bytes(p.B, self.L, p.n_all, self.Q)
+        ws = getattr(self, "_attach_ws", None)
+        if ws is None or ws.numel() < max(nbytes, 1):
+            ws = self._attach_ws = torch.empty(max(nbytes, 1), dtype=torch.uint8,
+                                               device=self.device)
+        score = torch.empty((p.B, p.n_all), dtype=torch.float32, device=self.device)
+        check(lib().trex_sankoff_attach(
+            ptr(p.attach_device(self.device)), ptr(leaves), ptr(cost), p.B, self.L, p.n_all,
+            self.Q, float(tau), ptr(dp), ptr(outside), ptr(new_leaf), ptr(sub_rows), ptr(score),
+            ptr(ws), ws.numel(), stream_handle(self.device)))
+        return score
+
     def value_and_grad(self, leaves, cost, tau: float = 0.0, d_tree_score=None,
                        hard_root=False):
         """(tree_score (B,), d_cost (Q, Q)) -- fused fwd + adjoint launch."""

@@ -115,20 +115,31 @@ def apply_nni(children, v: int, k: int) -> np.ndarray:
     a = kids[v]
     kids[v] = [s, a[1 - k]]
     kids[u] = [a[k], v]
-    # post-order renumbering, children in ascending id order
-    new_id = {c: c for c in range(nl)}
+    return _renumber(kids, n_all - 1, {c: c for c in range(nl)})
+
+
+def _renumber(kids, root, leaf_id, key=None) -> np.ndarray:
+    """Child lists of the tree ``kids`` (internal node -> its two children;
+    every other node is a leaf with the new id ``leaf_id[node]``): internal
+    nodes numbered in post-order by a DFS from ``root`` that visits children
+    in ascending ``key`` order (default: the node itself), each pair stored
+    ascending, the root last."""
+    key = key or (lambda node: node)
+    nl = len(leaf_id)
+    n_all = 2 * nl - 1
+    new_id = dict(leaf_id)
     out = np.full((n_all, 2), -1, dtype=np.int32)
     nxt = nl
-    stack = [(n_all - 1, False)]
+    stack = [(root, False)]
     while stack:
         node, done = stack.pop()
-        if node < nl:
+        if node not in kids:
             continue
         if not done:
             if len(stack) > 2 * n_all:
                 raise ValueError("children do not describe a tree")
             stack.append((node, True))
-            for c in sorted(kids[node], reverse=True):
+            for c in sorted(kids[node], key=key, reverse=True):
                 stack.append((c, False))
             continue
         if nxt >= n_all:
@@ -139,6 +150,67 @@ def apply_nni(children, v: int, k: int) -> np.ndarray:
     if nxt != n_all:
         raise ValueError("children do not describe a tree")
     return out
+
+
+def _proper_kids(children):
+    """{internal node: [c0, c1]} of one proper rooted binary tree's child
+    lists (what trex_nni_plan_build accepts); ValueError otherwise."""
+    ch = np.asarray(children)
+    if ch.ndim != 2 or ch.shape[1] != 2 or ch.shape[0] < 3 or ch.shape[0] % 2 == 0:
+        raise ValueError(f"children must be (n_all, 2) with n_all odd and >= 3, got {ch.shape}")
+    n_all = ch.shape[0]
+    nl = (n_all + 1) // 2
+    kids, seen = {}, set()
+    for node in range(nl, n_all):
+        c0, c1 = int(ch[node, 0]), int(ch[node, 1])
+        if not (0 <= c0 < node and 0 <= c1 < node) or c0 == c1 or c0 in seen or c1 in seen:
+            raise ValueError(f"children are not a proper rooted binary tree (node {node})")
+        seen.update((c0, c1))
+        kids[node] = [c0, c1]
+    return kids, nl, n_all
+
+
+def insert_leaf(children, x: int) -> np.ndarray:
+    """Child lists (n_all + 2, 2) of one tree after a new leaf is attached on
+    the edge above node ``x`` (``x = n_all - 1``: a new root above the old
+    one) -- the tree of ``SankoffEngine.attach_scores``' entry ``[x]``.
+
+    Old leaf ids are unchanged and the new leaf is ``n_leaves`` (the old
+    count).  Internal nodes are renumbered by ``apply_nni``'s rule; the DFS
+    orders children by their ids in the grown tree before renumbering: old
+    leaves keep theirs, the new leaf is ``n_leaves``, old internal node v is
+    v + 1, and the new internal node takes x's place among its parent's
+    children.
+    """
+    kids, nl, n_all = _proper_kids(children)
+    if not 0 <= x < n_all:
+        raise ValueError(f"x must be a node id in [0, {n_all}), got {x}")
+    up = lambda c: c if c < nl else c + 1  # noqa: E731
+    grown = {up(node): [up(c) for c in pair] for node, pair in kids.items()}
+    w = "w"
+    x_up = up(int(x))
+    grown[w] = [x_up, nl]
+    root = up(n_all - 1)
+    if x_up == root:
+        root = w
+    else:
+        for pair in grown.values():
+            if pair is not grown[w] and x_up in pair:
+                pair[pair.index(x_up)] = w
+    key = lambda node: (x_up, 1) if node == w else (node, 0)  # noqa: E731
+    return _renumber(grown, root, {c: c for c in range(nl + 1)}, key)
+
+
+def relabel_leaves(children, perm) -> np.ndarray:
+    """Child lists of one tree with leaf j renamed ``perm[j]`` (a permutation
+    of the leaf ids); internal nodes are renumbered by ``apply_nni``'s rule,
+    the DFS ordering children by their new leaf id / old internal id."""
+    kids, nl, n_all = _proper_kids(children)
+    perm = np.asarray(perm)
+    if perm.shape != (nl,) or sorted(perm.tolist()) != list(range(nl)):
+        raise ValueError(f"perm must be a permutation of 0..{nl - 1}")
+    leaf_id = {j: int(perm[j]) for j in range(nl)}
+    return _renumber(kids, n_all - 1, leaf_id, lambda node: leaf_id.get(node, node))
 
 
 class TreePlan:
@@ -173,6 +245,8 @@ class TreePlan:
         self._dev = {}
         self._nni_host = None
         self._nni_dev = {}
+        self._attach_host = None
+        self._attach_dev = {}
 
     # -- NNI plan (trex_nni_plan_build), built on first use ------------------
     @property
@@ -199,6 +273,31 @@ class TreePlan:
         if key not in self._nni_dev:
             self._nni_dev[key] = torch.from_numpy(self.nni_host).to(device)
         return self._nni_dev[key]
+
+    # -- attach plan (trex_attach_plan_build), built on first use -------------
+    @property
+    def attach_host(self) -> np.ndarray:
+        """The attach plan (include/trex_hip.h) as int32; TrexError as for
+        ``nni_host``."""
+        if self._attach_host is None:
+            L = lib()
+            n = L.trex_attach_plan_ints(self.B, self.n_all)
+            if n <= 0:
+                raise ValueError(f"bad attach plan shape B={self.B} n_all={self.n_all}")
+            buf = np.zeros(n, dtype=np.int32)
+            check(L.trex_attach_plan_build(self.children.ctypes.data, self.B, self.n_all,
+                                           buf.ctypes.data))
+            self._attach_host = buf
+        return self._attach_host
+
+    def attach_device(self, device):
+        """The attach plan as an int32 device tensor (cached per device)."""
+        import torch
+
+        key = str(device)
+        if key not in self._attach_dev:
+            self._attach_dev[key] = torch.from_numpy(self.attach_host).to(device)
+        return self._attach_dev[key]
 
     @property
     def nni_table(self) -> np.ndarray:
