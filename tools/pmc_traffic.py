@@ -61,12 +61,12 @@ def main():
         f = v.get("FETCH_SIZE", 0.0) * 1024 * fetch_corr
         w = v.get("WRITE_SIZE", 0.0) * 1024 * write_corr
         res["kernels"][s] = {"fetch_bytes": f, "write_bytes": w, "traffic_bytes": f + w}
-    # phase -> bench kernel name (sankoff_kernel<Q, SPT, SOFT, PHASE, RAGGED>)
+    # phase -> bench kernel name (sankoff_kernel<Q, SOFT, PHASE, RAGGED>)
     for s, e in res["kernels"].items():
         args = [x.strip() for x in s.split("<", 1)[1].rstrip(">").split(",")]
-        if len(args) > 4 and args[4] == "true":
+        if len(args) > 3 and args[3] == "true":
             continue  # ragged instantiation
-        ph = args[3]
+        ph = args[2]
         name = {"1": "sankoff_fwd", "2": "sankoff_bwd", "3": "sankoff_fwd_bwd"}.get(ph)
         if name:
             res[name] = e["traffic_bytes"]

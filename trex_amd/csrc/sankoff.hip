@@ -2,9 +2,10 @@
 //
 // Reference semantics: maraxen/trex src/trex/sankoff.py (run_dp :24-94,
 // vectorized_dp :97, run_sankoff :114-188, backtrack_sankoff_jit :191-267).
-// Design: one 64-lane wave per workgroup owns SPT*64 consecutive
-// sites of ONE tree, so every branch on the topology is wave-uniform and the
-// per-tree program (plan.cpp) is read with scalar loads.  Live internal DP
+// Design: one 64-lane wave per workgroup owns 64 consecutive
+// sites of ONE tree (one per lane), so every branch on the topology is
+// wave-uniform and the per-tree program (plan.cpp) is read with scalar loads.
+// Live internal DP
 // vectors / cotangents sit in a per-lane LDS stack (Sethi-Ullman slots);
 // the DP table is streamed to HBM with sites innermost (16/8-byte stores).
 // The cost matrix (and exp(-(C-cmin)/tau)) live in SGPRs.
@@ -13,9 +14,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
-#include <cstring>
 #include <mutex>
-#include <string>
 
 #include "sankoff_dev.h"
 #include "trex_common.h"
@@ -26,62 +25,10 @@ namespace {
 
 thread_local char g_err[512] = "no error";
 
-
-// --------------------------------------------------------------------------
-// per-lane vector helpers (SPT consecutive sites per lane)
-// --------------------------------------------------------------------------
-template <int SPT>
-__device__ __forceinline__ void ld(const float* __restrict__ p, float (&o)[SPT]) {
-  if constexpr (SPT == 4) {
-    const float4 v = *reinterpret_cast<const float4*>(p);
-    o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w;
-  } else if constexpr (SPT == 2) {
-    const float2 v = *reinterpret_cast<const float2*>(p);
-    o[0] = v.x; o[1] = v.y;
-  } else {
-    o[0] = *p;
-  }
-}
-
-template <int SPT>
-__device__ __forceinline__ void st(float* __restrict__ p, const float (&o)[SPT]) {
-  if constexpr (SPT == 4) {
-    *reinterpret_cast<float4*>(p) = make_float4(o[0], o[1], o[2], o[3]);
-  } else if constexpr (SPT == 2) {
-    *reinterpret_cast<float2*>(p) = make_float2(o[0], o[1]);
-  } else {
-    *p = o[0];
-  }
-}
-
-template <int SPT>
-__device__ __forceinline__ void ld_codes(const int8_t* __restrict__ p, int (&c)[SPT]) {
-  if constexpr (SPT == 4) {
-    const uint32_t w = *reinterpret_cast<const uint32_t*>(p);
-#pragma unroll
-    for (int s = 0; s < 4; ++s) c[s] = (int)(int8_t)(w >> (8 * s));
-  } else if constexpr (SPT == 2) {
-    const uint16_t w = *reinterpret_cast<const uint16_t*>(p);
-    c[0] = (int)(int8_t)(w & 0xFF);
-    c[1] = (int)(int8_t)(w >> 8);
-  } else {
-    c[0] = *p;
-  }
-}
-
-template <int SPT>
-__device__ __forceinline__ void st_codes(int8_t* __restrict__ p, const int (&c)[SPT]) {
-  if constexpr (SPT == 4) {
-    uint32_t w = 0;
-#pragma unroll
-    for (int s = 0; s < 4; ++s) w |= (uint32_t)(uint8_t)c[s] << (8 * s);
-    *reinterpret_cast<uint32_t*>(p) = w;
-  } else if constexpr (SPT == 2) {
-    *reinterpret_cast<uint16_t*>(p) = (uint16_t)((uint8_t)c[0] | ((uint8_t)c[1] << 8));
-  } else {
-    *p = (int8_t)c[0];
-  }
-}
+// one site's leaf code / ancestral state (int8 in memory); the __restrict__
+// tells the compiler that these bytes alias no DP row or LDS slot
+__device__ __forceinline__ int ld_code(const int8_t* __restrict__ p) { return *p; }
+__device__ __forceinline__ void st_code(int8_t* __restrict__ p, int c) { *p = (int8_t)c; }
 
 // --------------------------------------------------------------------------
 // cost matrix in SGPRs.  MODE: kHard (min-plus), kSoftK (factored softmin,
@@ -143,26 +90,8 @@ __device__ __forceinline__ void load_coef(const float* __restrict__ cost_, float
 // --------------------------------------------------------------------------
 // child value D_c (leaf row / LDS slot / dp row / 1e5 sentinel row)
 // --------------------------------------------------------------------------
-template <int Q, int SPT>
-__device__ __forceinline__ void leaf_rows(const int8_t* __restrict__ p, float (&d)[Q][SPT]) {
-  int code[SPT];
-  ld_codes<SPT>(p, code);
-#pragma unroll
-  for (int j = 0; j < Q; ++j)
-#pragma unroll
-    for (int s = 0; s < SPT; ++s) d[j][s] = (code[s] == j) ? 0.0f : kSentinel;
-}
-
-template <int Q, int SPT>
-__device__ __forceinline__ void fill_sentinel(float (&d)[Q][SPT]) {
-#pragma unroll
-  for (int j = 0; j < Q; ++j)
-#pragma unroll
-    for (int s = 0; s < SPT; ++s) d[j][s] = kSentinel;
-}
-
-// LDS slot stack: [slot][lane][Q][SPT] -- each lane's vector is contiguous,
-// so a slot access is Q*SPT/4 ds_read_b128 / ds_write_b128.
+// LDS slot stack: [slot][lane][Q] -- each lane's vector is contiguous, so a
+// slot access is one ds_read / ds_write of Q floats (b128 at Q = 4).
 template <int N>
 __device__ __forceinline__ void lds_vec_get(const float* p, float (&o)[N]) {
   if constexpr (N % 4 == 0) {
@@ -198,24 +127,22 @@ __device__ __forceinline__ void lds_vec_put(float* p, const float (&o)[N]) {
   }
 }
 
-template <int Q, int SPT>
-__device__ __forceinline__ void lds_get(const float* lds, int slot, int lane, float (&d)[Q][SPT]) {
-  float buf[Q * SPT];
-  lds_vec_get<Q * SPT>(lds + (slot * kWave + lane) * (Q * SPT), buf);
+// (both go through a local copy: the compiled kernels are the ones measured in
+// PERFLOG.md only in this form, see kSites)
+template <int Q>
+__device__ __forceinline__ void lds_get(const float* lds, int slot, int lane, float (&d)[Q]) {
+  float buf[Q];
+  lds_vec_get<Q>(lds + (slot * kWave + lane) * Q, buf);
 #pragma unroll
-  for (int j = 0; j < Q; ++j)
-#pragma unroll
-    for (int s = 0; s < SPT; ++s) d[j][s] = buf[j * SPT + s];
+  for (int j = 0; j < Q; ++j) d[j] = buf[j];
 }
 
-template <int Q, int SPT>
-__device__ __forceinline__ void lds_put(float* lds, int slot, int lane, const float (&d)[Q][SPT]) {
-  float buf[Q * SPT];
+template <int Q>
+__device__ __forceinline__ void lds_put(float* lds, int slot, int lane, const float (&d)[Q]) {
+  float buf[Q];
 #pragma unroll
-  for (int j = 0; j < Q; ++j)
-#pragma unroll
-    for (int s = 0; s < SPT; ++s) buf[j * SPT + s] = d[j][s];
-  lds_vec_put<Q * SPT>(lds + (slot * kWave + lane) * (Q * SPT), buf);
+  for (int j = 0; j < Q; ++j) buf[j] = d[j];
+  lds_vec_put<Q>(lds + (slot * kWave + lane) * Q, buf);
 }
 
 // C[i][code] from SGPR operands (code in [0, Q)); bit-tree select on SSA values
@@ -232,121 +159,22 @@ __device__ __forceinline__ float pick(const float (&row)[Q], int code) {
   return (code & 2) ? hi : lo;
 }
 
-
-template <int SPT>
-__device__ __forceinline__ void bst(rsrc_t r, int voff, int soff, const float (&o)[SPT]) {
-  if constexpr (SPT == 2) {
-    u32x2 w = {__float_as_uint(o[0]), __float_as_uint(o[1])};
-    __builtin_amdgcn_raw_buffer_store_b64(w, r, voff, soff, 0);
-  } else {
-    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(o[0]), r, voff, soff, 0);
-  }
-}
-
-template <int SPT>
-__device__ __forceinline__ void bld(rsrc_t r, int voff, int soff, float (&o)[SPT]) {
-  if constexpr (SPT == 2) {
-    const u32x2 w = __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, 0);
-    o[0] = __uint_as_float(w.x);
-    o[1] = __uint_as_float(w.y);
-  } else {
-    o[0] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0));
-  }
-}
-
-// Site-major DP rows ([row][L][Q]): a lane's SPT consecutive sites x Q states
-// are Q*SPT contiguous floats -> one dwordx4 (Q = 4), dwordx3 or dwordx2
-// access per site.  voff = site*Q*4 (per lane), soff = row*L*Q*4.
-#ifndef TREX_AUX_FWD
-#define TREX_AUX_FWD 2
-#endif
-#ifndef TREX_AUX_FUSED
-#define TREX_AUX_FUSED 0
-#endif
-#ifndef TREX_AUX_ADJ
-#define TREX_AUX_ADJ 2
-#endif
-#ifndef TREX_AUX_MARG
-#define TREX_AUX_MARG 2
-#endif
-// cache policy of the Q <= 4 kernel's DP-row accesses (2 = nt): the
-// forward-only kernel's row stores and the adjoint-only kernel's row reads
-// and marginal stores stream (C4 forward 620 -> 560 us, adjoint 588 -> ~577
-// us); the fused kernel re-reads its rows within the same wave's life, from
-// L2 / MALL in part, so its accesses stay temporal
-#ifndef TREX_AUX_LEAF
-#define TREX_AUX_LEAF 0  // the leaf-tile prefetch loads
-#endif
-#ifndef TREX_CHERRY_NT
-#define TREX_CHERRY_NT 2
-#endif
-constexpr int kAuxFwdRow = TREX_AUX_FWD, kAuxFusedRow = TREX_AUX_FUSED;
-#ifndef TREX_AUX_FUSED_LOAD
-#define TREX_AUX_FUSED_LOAD 2
-#endif
-// the fused kernel's adjoint re-reads of its own rows: nt (each row is read
-// once, then dead; with the never-re-read cherry rows also streamed, fused
-// 929-934 -> 903-911 us same box, PERFLOG; the stores stay temporal)
-constexpr int kAuxFusedLoad = TREX_AUX_FUSED_LOAD;
-// the fused kernel's stores of deferred-cherry rows (never re-read)
-constexpr int kAuxCherryRow = TREX_CHERRY_NT ? TREX_CHERRY_NT : TREX_AUX_FUSED;
-constexpr int kAuxAdjRow = TREX_AUX_ADJ, kAuxMarg = TREX_AUX_MARG;
-
-// AUX: the buffer instruction's cache-policy bits (2 = nt: a streaming
-// access that should not displace reused lines)
-template <int Q, int SPT, int AUX = 0>
-__device__ __forceinline__ void bst_row(rsrc_t r, int voff, int soff, const float (&d)[Q][SPT]) {
-#pragma unroll
-  for (int s = 0; s < SPT; ++s) {
-    const int vo = voff + s * Q * 4;
-    if constexpr (Q == 4) {
-      u32x4 w = {__float_as_uint(d[0][s]), __float_as_uint(d[1][s]), __float_as_uint(d[2][s]),
-                 __float_as_uint(d[3][s])};
-      __builtin_amdgcn_raw_buffer_store_b128(w, r, vo, soff, AUX);
-    } else if constexpr (Q == 3) {
-      u32x3 w = {__float_as_uint(d[0][s]), __float_as_uint(d[1][s]), __float_as_uint(d[2][s])};
-      __builtin_amdgcn_raw_buffer_store_b96(w, r, vo, soff, AUX);
-    } else {
-      u32x2 w = {__float_as_uint(d[0][s]), __float_as_uint(d[1][s])};
-      __builtin_amdgcn_raw_buffer_store_b64(w, r, vo, soff, AUX);
-    }
-  }
-}
-
-template <int Q, int SPT, int AUX = 0>
-__device__ __forceinline__ void bld_row(rsrc_t r, int voff, int soff, float (&d)[Q][SPT]) {
-#pragma unroll
-  for (int s = 0; s < SPT; ++s) {
-    const int vo = voff + s * Q * 4;
-    if constexpr (Q == 4) {
-      const u32x4 w = __builtin_amdgcn_raw_buffer_load_b128(r, vo, soff, AUX);
-      d[0][s] = __uint_as_float(w.x); d[1][s] = __uint_as_float(w.y);
-      d[2][s] = __uint_as_float(w.z); d[3][s] = __uint_as_float(w.w);
-    } else if constexpr (Q == 3) {
-      const u32x3 w = __builtin_amdgcn_raw_buffer_load_b96(r, vo, soff, AUX);
-      d[0][s] = __uint_as_float(w.x); d[1][s] = __uint_as_float(w.y); d[2][s] = __uint_as_float(w.z);
-    } else {
-      const u32x2 w = __builtin_amdgcn_raw_buffer_load_b64(r, vo, soff, AUX);
-      d[0][s] = __uint_as_float(w.x); d[1][s] = __uint_as_float(w.y);
-    }
-  }
-}
-
-#ifdef TREX_DIAG_PAD
-// sensitivity probe (diagnostic builds only, wrong timing on purpose, same
-// results): TREX_DIAG_SALU / TREX_DIAG_VALU independent dummy scalar /
-// vector adds per tree step, to see which issue stream the time follows
-__device__ __forceinline__ void diag_pad(float& v) {
-  int sd = 0;
-#pragma unroll
-  for (int i = 0; i < TREX_DIAG_SALU; ++i) asm volatile("s_add_u32 %0, %0, 1" : "+s"(sd));
-  float t = 0.0f;
-#pragma unroll
-  for (int i = 0; i < TREX_DIAG_VALU; ++i) asm volatile("v_add_f32 %0, 1.0, %0" : "+v"(t));
-  asm volatile("" ::"s"(sd), "v"(t));
-  (void)v;
-}
-#endif
+// Cache policy (the buffer instructions' aux bits, 2 = nt; bld_row / bst_row,
+// sankoff_dev.h) of the DP-row accesses.  Each value won its A/B (PERFLOG.md):
+constexpr int kAuxFwdRow = 2;     // forward-only row stores stream: C4 forward 620 -> 560 us
+constexpr int kAuxAdjRow = 2;     // adjoint-only row reads stream: C4 adjoint 588 -> ~577 us
+constexpr int kAuxMarg = 2;       // marginal stores stream (never re-read by the kernel)
+constexpr int kAuxFusedRow = 0;   // fused stores stay temporal: all-nt, 128-tree shard 128 -> 135 us
+constexpr int kAuxFusedLoad = 2;  // fused re-reads (read once, then dead): 929-934 -> 903-911 us
+constexpr int kAuxCherryRow = 2;  // fused deferred-cherry rows (never re-read): shard 134 -> 128 us
+constexpr int kAuxLeaf = 0;       // leaf-tile prefetch loads: nt made the forward 521 -> 643 us
+// waves per SIMD asked of the compiler (amdgpu_waves_per_eu), per phase
+constexpr int kFwdWpe = 6;    // forward-only (LDS-bound at C4)
+constexpr int kAdjWpe = 5;    // adjoint-only: 6 spills (235 vs 171 us), 7 too (fused 1 015 -> 1 077)
+constexpr int kFusedWpe = 5;  // fused: 6 or 4 waves measured 958-1 155 vs 934-943 us
+constexpr int kFusedWpeMax = 8;
+// adjoint DP-row prefetch depth (steps): 2 -> 3 C4 fused 1 015 -> 988 us, 4 no further gain
+constexpr int kAdjRing = 3;
 
 // s_i = sum_j K_ij u_j for every parent state i.  SYM (K = K^T, symmetric
 // C): s_i = sum_j K_ji u_j, accumulated over j with the row pairs (K_j,2p,
@@ -377,52 +205,45 @@ __device__ __forceinline__ void kvec(const Coef<Q>& cf, const float (&u)[Q], flo
 // --------------------------------------------------------------------------
 // message M_c[i] = min_j / smin_j (C[i][j] + D_c[j])      (sankoff.py:67-68)
 // --------------------------------------------------------------------------
-template <int Q, int SPT, int MODE, bool SYM = false>
+template <int Q, int MODE, bool SYM = false>
 __device__ __forceinline__ void message(const Coef<Q>& cf, float a, float bcoef,
-                                        const float (&d)[Q][SPT], float (&m)[Q][SPT]) {
+                                        const float (&d)[Q], float (&m)[Q]) {
   if constexpr (MODE == kHard) {
 #pragma unroll
-    for (int i = 0; i < Q; ++i)
+    for (int i = 0; i < Q; ++i) {
+      float v = cf.c[i][0] + d[0];
 #pragma unroll
-      for (int s = 0; s < SPT; ++s) {
-        float v = cf.c[i][0] + d[0][s];
-#pragma unroll
-        for (int j = 1; j < Q; ++j) v = fminf(v, cf.c[i][j] + d[j][s]);
-        m[i][s] = v;
-      }
-  } else if constexpr (MODE == kSoftK) {
-#pragma unroll
-    for (int s = 0; s < SPT; ++s) {
-      float md = d[0][s];
-#pragma unroll
-      for (int j = 1; j < Q; ++j) md = fminf(md, d[j][s]);
-      const float mda = md * a;
-      float u[Q];
-#pragma unroll
-      for (int j = 0; j < Q; ++j) u[j] = fast_exp2(fmaf(-d[j][s], a, mda));
-      const float base = md + cf.cmin;
-      float sv[Q];
-      kvec<Q, SYM>(cf, u, sv);
-#pragma unroll
-      for (int i = 0; i < Q; ++i) m[i][s] = fmaf(-bcoef, fast_log2(sv[i]), base);
+      for (int j = 1; j < Q; ++j) v = fminf(v, cf.c[i][j] + d[j]);
+      m[i] = v;
     }
+  } else if constexpr (MODE == kSoftK) {
+    float md = d[0];
+#pragma unroll
+    for (int j = 1; j < Q; ++j) md = fminf(md, d[j]);
+    const float mda = md * a;
+    float u[Q];
+#pragma unroll
+    for (int j = 0; j < Q; ++j) u[j] = fast_exp2(fmaf(-d[j], a, mda));
+    const float base = md + cf.cmin;
+    float sv[Q];
+    kvec<Q, SYM>(cf, u, sv);
+#pragma unroll
+    for (int i = 0; i < Q; ++i) m[i] = fmaf(-bcoef, fast_log2(sv[i]), base);
   } else {
 #pragma unroll
-    for (int i = 0; i < Q; ++i)
+    for (int i = 0; i < Q; ++i) {
+      float x[Q];
+      float mn = INFINITY;
 #pragma unroll
-      for (int s = 0; s < SPT; ++s) {
-        float x[Q];
-        float mn = INFINITY;
-#pragma unroll
-        for (int j = 0; j < Q; ++j) {
-          x[j] = cf.c[i][j] + d[j][s];
-          mn = fminf(mn, x[j]);
-        }
-        float acc = 0.0f;
-#pragma unroll
-        for (int j = 0; j < Q; ++j) acc += fast_exp2((mn - x[j]) * a);
-        m[i][s] = fmaf(-bcoef, fast_log2(acc), mn);
+      for (int j = 0; j < Q; ++j) {
+        x[j] = cf.c[i][j] + d[j];
+        mn = fminf(mn, x[j]);
       }
+      float acc = 0.0f;
+#pragma unroll
+      for (int j = 0; j < Q; ++j) acc += fast_exp2((mn - x[j]) * a);
+      m[i] = fmaf(-bcoef, fast_log2(acc), mn);
+    }
   }
 }
 
@@ -471,109 +292,94 @@ __device__ __forceinline__ void softk_edge(const Coef<Q>& cf, const float (&u)[Q
 // In the factored softmin acc holds sum r_i u_j; the K[i][j] factor is
 // applied once in the final reduction.
 // --------------------------------------------------------------------------
-template <int Q, int SPT, int MODE, bool SYM = false>
-__device__ __forceinline__ void message_adjoint(const Coef<Q>& cf, float a,
-                                                const float (&d)[Q][SPT],
-                                                const float (&g)[Q][SPT],
-                                                float (&acc)[Q][Q], float (&gc)[Q][SPT]) {
+template <int Q, int MODE, bool SYM = false>
+__device__ __forceinline__ void message_adjoint(const Coef<Q>& cf, float a, const float (&d)[Q],
+                                                const float (&g)[Q], float (&acc)[Q][Q],
+                                                float (&gc)[Q]) {
+  if constexpr (MODE == kHard) {
 #pragma unroll
-  for (int s = 0; s < SPT; ++s) {
-    if constexpr (MODE == kHard) {
+    for (int j = 0; j < Q; ++j) gc[j] = 0.0f;
 #pragma unroll
-      for (int j = 0; j < Q; ++j) gc[j][s] = 0.0f;
+    for (int i = 0; i < Q; ++i) {
+      float x[Q];
+      float mn = cf.c[i][0] + d[0];
+      x[0] = mn;
 #pragma unroll
-      for (int i = 0; i < Q; ++i) {
-        float x[Q];
-        float mn = cf.c[i][0] + d[0][s];
-        x[0] = mn;
-#pragma unroll
-        for (int j = 1; j < Q; ++j) {
-          x[j] = cf.c[i][j] + d[j][s];
-          mn = fminf(mn, x[j]);
-        }
-        float cnt = 0.0f;
-#pragma unroll
-        for (int j = 0; j < Q; ++j) cnt += (x[j] == mn) ? 1.0f : 0.0f;
-        const float r = g[i][s] / cnt;
-#pragma unroll
-        for (int j = 0; j < Q; ++j) {
-          const float w = (x[j] == mn) ? r : 0.0f;
-          acc[i][j] += w;
-          gc[j][s] += w;
-        }
+      for (int j = 1; j < Q; ++j) {
+        x[j] = cf.c[i][j] + d[j];
+        mn = fminf(mn, x[j]);
       }
-    } else if constexpr (MODE == kSoftK) {
-      float ds[Q], gs[Q], u[Q], rs[Q], gcs[Q];
+      float cnt = 0.0f;
+#pragma unroll
+      for (int j = 0; j < Q; ++j) cnt += (x[j] == mn) ? 1.0f : 0.0f;
+      const float r = g[i] / cnt;
 #pragma unroll
       for (int j = 0; j < Q; ++j) {
-        ds[j] = d[j][s];
-        gs[j] = g[j][s];
+        const float w = (x[j] == mn) ? r : 0.0f;
+        acc[i][j] += w;
+        gc[j] += w;
       }
-      softk_weights<Q, SYM>(cf, a, ds, u, rs);
-      softk_edge<Q>(cf, u, rs, gs, acc, gcs);
+    }
+  } else if constexpr (MODE == kSoftK) {
+    float u[Q], rs[Q];
+    softk_weights<Q, SYM>(cf, a, d, u, rs);
+    softk_edge<Q>(cf, u, rs, g, acc, gc);
+  } else {
 #pragma unroll
-      for (int j = 0; j < Q; ++j) gc[j][s] = gcs[j];
-    } else {
+    for (int j = 0; j < Q; ++j) gc[j] = 0.0f;
 #pragma unroll
-      for (int j = 0; j < Q; ++j) gc[j][s] = 0.0f;
+    for (int i = 0; i < Q; ++i) {
+      float x[Q];
+      float mn = INFINITY;
 #pragma unroll
-      for (int i = 0; i < Q; ++i) {
-        float x[Q];
-        float mn = INFINITY;
+      for (int j = 0; j < Q; ++j) {
+        x[j] = cf.c[i][j] + d[j];
+        mn = fminf(mn, x[j]);
+      }
+      float e[Q];
+      float sm = 0.0f;
 #pragma unroll
-        for (int j = 0; j < Q; ++j) {
-          x[j] = cf.c[i][j] + d[j][s];
-          mn = fminf(mn, x[j]);
-        }
-        float e[Q];
-        float sm = 0.0f;
+      for (int j = 0; j < Q; ++j) {
+        e[j] = fast_exp2((mn - x[j]) * a);
+        sm += e[j];
+      }
+      const float r = g[i] * __builtin_amdgcn_rcpf(sm);
 #pragma unroll
-        for (int j = 0; j < Q; ++j) {
-          e[j] = fast_exp2((mn - x[j]) * a);
-          sm += e[j];
-        }
-        const float r = g[i][s] * __builtin_amdgcn_rcpf(sm);
-#pragma unroll
-        for (int j = 0; j < Q; ++j) {
-          const float w = r * e[j];
-          acc[i][j] += w;
-          gc[j][s] += w;
-        }
+      for (int j = 0; j < Q; ++j) {
+        const float w = r * e[j];
+        acc[i][j] += w;
+        gc[j] += w;
       }
     }
   }
 }
 
 // root: score and cotangent of the per-site score      (sankoff.py:187)
-template <int Q, int SPT, bool SOFT>
-__device__ __forceinline__ void root_score(const float (&d)[Q][SPT], float a, float bcoef,
-                                           bool hard_root, float (&score)[SPT],
-                                           float (&w)[Q][SPT]) {
+template <int Q, bool SOFT>
+__device__ __forceinline__ void root_score(const float (&d)[Q], float a, float bcoef,
+                                           bool hard_root, float& score, float (&w)[Q]) {
+  float mn = d[0];
 #pragma unroll
-  for (int s = 0; s < SPT; ++s) {
-    float mn = d[0][s];
+  for (int i = 1; i < Q; ++i) mn = fminf(mn, d[i]);
+  if (!SOFT || hard_root) {
+    float cnt = 0.0f;
 #pragma unroll
-    for (int i = 1; i < Q; ++i) mn = fminf(mn, d[i][s]);
-    if (!SOFT || hard_root) {
-      float cnt = 0.0f;
+    for (int i = 0; i < Q; ++i) cnt += (d[i] == mn) ? 1.0f : 0.0f;
+    const float r = 1.0f / cnt;
 #pragma unroll
-      for (int i = 0; i < Q; ++i) cnt += (d[i][s] == mn) ? 1.0f : 0.0f;
-      const float r = 1.0f / cnt;
+    for (int i = 0; i < Q; ++i) w[i] = (d[i] == mn) ? r : 0.0f;
+    score = mn;
+  } else {
+    float sm = 0.0f;
 #pragma unroll
-      for (int i = 0; i < Q; ++i) w[i][s] = (d[i][s] == mn) ? r : 0.0f;
-      score[s] = mn;
-    } else {
-      float sm = 0.0f;
-#pragma unroll
-      for (int i = 0; i < Q; ++i) {
-        w[i][s] = fast_exp2((mn - d[i][s]) * a);
-        sm += w[i][s];
-      }
-      const float r = __builtin_amdgcn_rcpf(sm);
-#pragma unroll
-      for (int i = 0; i < Q; ++i) w[i][s] *= r;
-      score[s] = fmaf(-bcoef, fast_log2(sm), mn);
+    for (int i = 0; i < Q; ++i) {
+      w[i] = fast_exp2((mn - d[i]) * a);
+      sm += w[i];
     }
+    const float r = __builtin_amdgcn_rcpf(sm);
+#pragma unroll
+    for (int i = 0; i < Q; ++i) w[i] *= r;
+    score = fmaf(-bcoef, fast_log2(sm), mn);
   }
 }
 
@@ -581,9 +387,9 @@ __device__ __forceinline__ void root_score(const float (&d)[Q][SPT], float a, fl
 // --------------------------------------------------------------------------
 // Unified Sankoff kernel: PHASE 1 = forward, 2 = adjoint, 3 = both (fused).
 //
-// One wave per workgroup = 64*SPT consecutive sites of one tree.  LDS holds
-//   [slots][Q][64][SPT] f32  live D vectors (forward) / cotangents (adjoint)
-//   [nl][64][SPT]       i8   the tile's leaf states (prologue prefetch)
+// One wave per workgroup = 64 consecutive sites of one tree.  LDS holds
+//   [slots][64][Q] f32  live D vectors (forward) / cotangents (adjoint)
+//   [nl][64]       i8   the tile's leaf states (prologue prefetch)
 // Leaf and sentinel children are lookups in per-code tables (message and
 // adjoint weights; exact closed forms C[i][code] / one-hot when the 1e5
 // sentinel dominates), i.e. no transcendental for half of all children.
@@ -621,7 +427,7 @@ struct KArgs {
 // 0, W[code][i][j] = its adjoint weight (divided by K_ij in the factored
 // form) at kWTab -- both depend on the code only, so every leaf / sentinel
 // child is a table lookup in both sweeps; then the slot stack
-// [max(n_slots, 1)][64][Q*SPT], then the leaf tile [nl][64*SPT] i8 (raw
+// [max(n_slots, 1)][64][Q], then the leaf tile [nl][64] i8 (raw
 // codes, normalised to [0, Q] at use).  The root's cotangent goes to slot 0:
 // it is written after the forward has consumed every slot and read by the
 // first reverse step (always the root's), before any child cotangent is
@@ -650,37 +456,31 @@ constexpr int kPairFwd = 28;      // forward-only: TM at [28, 128)
 constexpr int tab_floats(int phase) {
   return kLeafTabFloats + ((kPairTables && phase != 1) ? 3 * kPairFloats : 0);
 }
-#ifndef TREX_ADJ_RING
-#define TREX_ADJ_RING 3
-#endif
-#ifndef TREX_ADJ_WPE
-#define TREX_ADJ_WPE 5
-#endif
-#ifndef TREX_FUSED_WPE
-#define TREX_FUSED_WPE TREX_ADJ_WPE
-#endif
-#ifndef TREX_FUSED_WPE_MAX
-#define TREX_FUSED_WPE_MAX 8
-#endif
-#ifndef TREX_FWD_WPE
-#define TREX_FWD_WPE 6
-#endif
-constexpr int kAdjRing = TREX_ADJ_RING;  // adjoint DP-row prefetch depth (steps)
+// Sites per lane.  Only one was ever built (two doubled the adjoint's VGPRs
+// and were slower at every grid measured) and the code
+// carries no second one.  The one-trip `for (s < kSites)` loops that remain in
+// sankoff_body, and a few copies through a local array (r, mv, buf), are there
+// for the compiler alone: each leaves blocks behind that decide block order,
+// the grouping of the scalar step-word loads and register numbering, and
+// without any one of them the forward-bearing or Q = 3 kernels come out as
+// other machine code than the one every figure in PERFLOG.md was measured on
+// (PERFLOG.md, "sites-per-lane axis" section, has the experiment).  Drop them
+// only together with an A/B of all 36 kernels.
+constexpr int kSites = 1;
 constexpr int kPrefetchRows = 64;  // leaf tiles of <= 64 leaves are prefetched
 
 // Persistent waves: the grid holds as many waves as are co-resident; block
 // (x = blockIdx % 8, j = blockIdx / 8) walks the items of XCD x's contiguous
 // range with stride gridDim/8, so the waves of one XCD always work on
-// adjacent tiles (shared L2 lines).  Each item is one (tree, 64*SPT-site
-// tile); the next item's leaf tile is loaded into registers while the
-// current one computes.
+// adjacent tiles (shared L2 lines).  Each item is one (tree, 64-site tile);
+// the next item's leaf tile is loaded into registers while the current one
+// computes.
 // (An LDS-resident fused variant -- every internal D vector of the tree kept
 // in LDS, no adjoint re-read, one wave per SIMD -- measured 2.3x slower on the
 // C4 shard and on par for C2; removed in round 3 with the other A/B-only
 // variants)
-template <int Q, int SPT, int MODE, int PHASE, bool RAGGED, bool SYM = false>
+template <int Q, int MODE, int PHASE, bool RAGGED, bool SYM = false>
 __device__ __forceinline__ void sankoff_body(const KArgs& A, float* lds) {
-  static_assert(!RAGGED || SPT == 1, "ragged batches use the SPT=1 kernels");
   constexpr bool SOFT = MODE != kHard;
   constexpr bool FWD = (PHASE & 1) != 0;
   constexpr bool BWD = (PHASE & 2) != 0;
@@ -706,7 +506,7 @@ __device__ __forceinline__ void sankoff_body(const KArgs& A, float* lds) {
   float* tr = tab + kLeafTabFloats + 2 * kPairFloats;
   constexpr bool PAIR_ADJ = kPairTables && BWD && MODE == kSoftK;
   constexpr int kRootSlot = 0;
-  int8_t* lleaf = reinterpret_cast<int8_t*>(slots + (size_t)max(A.n_slots, 1) * Q * kWave * SPT);
+  int8_t* lleaf = reinterpret_cast<int8_t*>(slots + (size_t)max(A.n_slots, 1) * Q * kWave);
 
   // ---- once per wave: the leaf tables.  Lane c <= Q builds row c from the
   // child row D = (0 at c, 1e5 elsewhere; all 1e5 for c = Q).  When the 1e5
@@ -722,11 +522,11 @@ __device__ __forceinline__ void sankoff_body(const KArgs& A, float* lds) {
     const bool lfast = (MODE != kHard) ? ((kSentinel - range) * a >= 64.0f) : (range < 99000.0f);
     if (lane <= Q) {
       const cptr<float> cost = as_const(A.cost);
-      float d1[Q][1], m1[Q][1], g1[Q][1], w1[Q][Q], gc1[Q][1];
+      float d1[Q], m1[Q], g1[Q], w1[Q][Q], gc1[Q];
 #pragma unroll
       for (int j = 0; j < Q; ++j) {
-        d1[j][0] = j == lane ? 0.0f : kSentinel;
-        g1[j][0] = 1.0f;
+        d1[j] = j == lane ? 0.0f : kSentinel;
+        g1[j] = 1.0f;
       }
 #pragma unroll
       for (int i = 0; i < Q; ++i)
@@ -736,18 +536,18 @@ __device__ __forceinline__ void sankoff_body(const KArgs& A, float* lds) {
 #pragma unroll
         for (int i = 0; i < Q; ++i) {
           const float cv = cost[i * Q + lane];
-          m1[i][0] = cv;
+          m1[i] = cv;
           const float ik = MODE == kSoftK ? fast_exp2((cv - cf.cmin) * a) : 1.0f;
 #pragma unroll
           for (int j = 0; j < Q; ++j) w1[i][j] = j == lane ? ik : 0.0f;
         }
       } else {
-        message<Q, 1, MODE>(cf, a, bcoef, d1, m1);
-        if constexpr (BWD) message_adjoint<Q, 1, MODE>(cf, a, d1, g1, w1, gc1);
+        message<Q, MODE>(cf, a, bcoef, d1, m1);
+        if constexpr (BWD) message_adjoint<Q, MODE>(cf, a, d1, g1, w1, gc1);
       }
 #pragma unroll
       for (int i = 0; i < Q; ++i) {
-        tab[lane * Q + i] = m1[i][0];
+        tab[lane * Q + i] = m1[i];
         if constexpr (BWD) {  // the forward-only kernel has no W (TM lies there)
 #pragma unroll
           for (int j = 0; j < Q; ++j) tab[kWTab + (lane * Q + i) * Q + j] = w1[i][j];
@@ -762,23 +562,21 @@ __device__ __forceinline__ void sankoff_body(const KArgs& A, float* lds) {
     __syncthreads();  // T is written by lanes <= Q
     if (lane < (Q + 1) * (Q + 1)) {
       const int c0 = lane / (Q + 1), c1 = lane - c0 * (Q + 1);
-      float t0[Q], t1[Q], d1[Q][1];
+      float t0[Q], t1[Q], d1[Q];
       lds_vec_get<Q>(tab + c0 * Q, t0);
       lds_vec_get<Q>(tab + c1 * Q, t1);
 #pragma unroll
-      for (int j = 0; j < Q; ++j) d1[j][0] = t0[j] + t1[j];
+      for (int j = 0; j < Q; ++j) d1[j] = t0[j] + t1[j];
       if constexpr (FWD) {
-        float m1[Q][1], mv[Q];
-        message<Q, 1, MODE, false>(cf, a, bcoef, d1, m1);
+        float m1[Q], mv[Q];
+        message<Q, MODE, false>(cf, a, bcoef, d1, m1);
 #pragma unroll
-        for (int i = 0; i < Q; ++i) mv[i] = m1[i][0];
+        for (int i = 0; i < Q; ++i) mv[i] = m1[i];
         lds_vec_put<Q>(tm + lane * Q, mv);
       }
       if constexpr (PAIR_ADJ) {
-        float ds[Q], u[Q], rs[Q];
-#pragma unroll
-        for (int j = 0; j < Q; ++j) ds[j] = d1[j][0];
-        softk_weights<Q, SYM>(cf, a, ds, u, rs);
+        float u[Q], rs[Q];
+        softk_weights<Q, SYM>(cf, a, d1, u, rs);
         lds_vec_put<Q>(tu + lane * Q, u);
         lds_vec_put<Q>(tr + lane * Q, rs);
       }
@@ -792,7 +590,7 @@ __device__ __forceinline__ void sankoff_body(const KArgs& A, float* lds) {
   // kernel loops over items and so prefetches the NEXT tile: the adjoint's
   // register footprint is too large to keep a second tile in flight
   constexpr bool PERSIST = PHASE == 1;
-  const bool pf = !RAGGED && SPT == 1 && (L & 3) == 0 && A.nl <= kPrefetchRows;
+  const bool pf = !RAGGED && (L & 3) == 0 && A.nl <= kPrefetchRows;
   const int pf_voff = (lane >> 4) * L + (lane & 15) * 4;
   uint32_t pre[kPrefetchRows / 4];
   auto issue_prefetch = [&](int it) {
@@ -801,7 +599,7 @@ __device__ __forceinline__ void sankoff_body(const KArgs& A, float* lds) {
     const rsrc_t rl = make_rsrc(A.leaves + (size_t)tr * A.nl * L, (uint32_t)((size_t)A.nl * L));
 #pragma unroll
     for (int r = 0; r < kPrefetchRows / 4; ++r)
-      pre[r] = __builtin_amdgcn_raw_buffer_load_b32(rl, pf_voff, 4 * r * L + tl * kWave, TREX_AUX_LEAF);
+      pre[r] = __builtin_amdgcn_raw_buffer_load_b32(rl, pf_voff, 4 * r * L + tl * kWave, kAuxLeaf);
   };
   auto store_prefetch = [&]() {
     uint32_t* dst = reinterpret_cast<uint32_t*>(lleaf);
@@ -841,7 +639,7 @@ __device__ __forceinline__ void sankoff_body(const KArgs& A, float* lds) {
       site_base = (size_t)tree * L;
       prog = as_const(reinterpret_cast<const int*>(A.steps)) + (size_t)tree * A.n_int * 4;
     }
-    const int site = (tile * kWave + lane) * SPT;
+    const int site = tile * kWave + lane;
     const bool active = site < Lt;
     const int sc = active ? site : 0;
 
@@ -853,14 +651,14 @@ __device__ __forceinline__ void sankoff_body(const KArgs& A, float* lds) {
       const int8_t* lv = A.leaves + leaf_base + sc;
       constexpr int kBatch = 8;
       for (int c0 = 0; c0 < nl; c0 += kBatch) {
-        int code[kBatch][SPT];
+        int code[kBatch];
         const int nb_ = min(kBatch, nl - c0);
 #pragma unroll
         for (int u = 0; u < kBatch; ++u)
-          if (u < nb_) ld_codes<SPT>(lv + (size_t)(c0 + u) * Lt, code[u]);
+          if (u < nb_) code[u] = ld_code(lv + (size_t)(c0 + u) * Lt);
 #pragma unroll
         for (int u = 0; u < kBatch; ++u)
-          if (u < nb_) st_codes<SPT>(lleaf + ((c0 + u) * kWave + lane) * SPT, code[u]);
+          if (u < nb_) st_code(lleaf + ((c0 + u) * kWave + lane), code[u]);
       }
     }
 
@@ -870,24 +668,35 @@ __device__ __forceinline__ void sankoff_body(const KArgs& A, float* lds) {
     const int voff = active ? site * Q * 4 : 0x7FFFFFF0;
     const int rowbytes = Lt * Q * 4;
 
-    auto child_code = [&](int desc, int (&code)[SPT]) {
-      ld_codes<SPT>(lleaf + ((desc & 0xFFFF) * kWave + lane) * SPT, code);
+    // a child's leaf code normalised to [0, Q] (Q: missing leaf / the all-1e5
+    // row): leaf_code of a leaf child, child_code of a leaf or sentinel child
+    auto leaf_code = [&](int desc, int& code) {
+      code = ld_code(lleaf + ((desc & 0xFFFF) * kWave + lane));
+      code = ((unsigned)code < (unsigned)Q) ? code : Q;
+    };
+    auto child_code = [&](int desc, int kind) {
+      int code;
+      if (kind == kKindLeaf) {
+        leaf_code(desc, code);
+      } else {
 #pragma unroll
-      for (int s = 0; s < SPT; ++s) code[s] = ((unsigned)code[s] < (unsigned)Q) ? code[s] : Q;
+        for (int s = 0; s < kSites; ++s) code = Q;
+      }
+      return code;
     };
 
-    float dv[Q][SPT];
+    float dv[Q];
     if constexpr (FWD) {
-      float prev[Q][SPT];  // previous step's D (register bypass, kChildPrev)
+      float prev[Q];  // previous step's D (register bypass, kChildPrev)
       I4 nxt = load_step(prog, 0);
       for (int k = 0; k < n_int; ++k) {
         const I4 stp = nxt;
         if (k + 1 < n_int) nxt = load_step(prog, k + 1);
         // gather both children (LDS reads in flight together)
-        float d[2][Q][SPT];
-        int pair[SPT];  // c0 (Q + 1) + c1 of a step whose children are both codes
+        float d[2][Q];
+        int pair;  // c0 (Q + 1) + c1 of a step whose children are both codes
 #pragma unroll
-        for (int s = 0; s < SPT; ++s) pair[s] = 0;
+        for (int s = 0; s < kSites; ++s) pair = 0;
 #pragma unroll
         for (int c = 0; c < 2; ++c) {
           const int desc = c == 0 ? stp.y : stp.z;
@@ -896,102 +705,88 @@ __device__ __forceinline__ void sankoff_body(const KArgs& A, float* lds) {
 #pragma unroll
             for (int j = 0; j < Q; ++j)
 #pragma unroll
-              for (int s = 0; s < SPT; ++s) d[c][j][s] = prev[j][s];
+              for (int s = 0; s < kSites; ++s) d[c][j] = prev[j];
           } else if (kind == kKindInt) {
-            lds_get<Q, SPT>(slots, (desc >> 16) & 0xFF, lane, d[c]);
+            lds_get<Q>(slots, (desc >> 16) & 0xFF, lane, d[c]);
           } else {
-            int code[SPT];
+            int code;  // child_code(desc, kind), spelled out (see kSites)
             if (kind == kKindLeaf) {
-              child_code(desc, code);
+              leaf_code(desc, code);
             } else {
 #pragma unroll
-              for (int s = 0; s < SPT; ++s) code[s] = Q;  // all-1e5 row
+              for (int s = 0; s < kSites; ++s) code = Q;
             }
 #pragma unroll
-            for (int s = 0; s < SPT; ++s) {
+            for (int s = 0; s < kSites; ++s) {
               float r[Q];
-              lds_vec_get<Q>(tab + code[s] * Q, r);
+              lds_vec_get<Q>(tab + code * Q, r);
 #pragma unroll
-              for (int i = 0; i < Q; ++i) d[c][i][s] = r[i];  // already the message
-              if constexpr (kPairTables) pair[s] = c == 0 ? code[s] * (Q + 1) : pair[s] + code[s];
+              for (int i = 0; i < Q; ++i) d[c][i] = r[i];  // already the message
+              if constexpr (kPairTables) pair = c == 0 ? code * (Q + 1) : pair + code;
             }
           }
         }
 #pragma unroll
         for (int c = 0; c < 2; ++c) {
           const int desc = c == 0 ? stp.y : stp.z;
-          float m[Q][SPT];
+          float m[Q];
           // a deferred cherry handed its message on (TM), not its D
           if (((desc >> 24) & 3) != kKindInt || (kPairTables && (desc & kChildDeferred))) {
 #pragma unroll
             for (int i = 0; i < Q; ++i)
 #pragma unroll
-              for (int s = 0; s < SPT; ++s) m[i][s] = d[c][i][s];
+              for (int s = 0; s < kSites; ++s) m[i] = d[c][i];
           } else {
             // the forward keeps the pair-wise dots in every kernel: the DP
             // table is bitwise the same from the fused, forward-only and
             // ragged launches (the symmetric-K form sums in another order)
-            message<Q, SPT, MODE, false>(cf, a, bcoef, d[c], m);
+            message<Q, MODE, false>(cf, a, bcoef, d[c], m);
           }
 #pragma unroll
           for (int i = 0; i < Q; ++i)
 #pragma unroll
-            for (int s = 0; s < SPT; ++s) dv[i][s] = (c == 0) ? m[i][s] : dv[i][s] + m[i][s];
+            for (int s = 0; s < kSites; ++s) dv[i] = (c == 0) ? m[i] : dv[i] + m[i];
         }
         const int row = stp.x & 0xFFFF;
         const int oslot = (stp.x >> 16) & 0xFF;
-#ifdef TREX_DIAG_PAD
-        diag_pad(dv[0][0]);
-#endif
-#ifdef TREX_DIAG_NOSTORE
-        bst_row<Q, SPT, BWD ? kAuxFusedRow : kAuxFwdRow>(rdp, 0x7FFFFFF0, row * rowbytes, dv);
-#elif defined(TREX_DIAG_DROP)
-        // probe: the first (DROP > 0) or last (DROP < 0) |DROP| steps' stores dropped
-        const bool drop = TREX_DIAG_DROP > 0 ? k < TREX_DIAG_DROP : k >= n_int + TREX_DIAG_DROP;
-        bst_row<Q, SPT, BWD ? kAuxFusedRow : kAuxFwdRow>(rdp, drop ? 0x7FFFFFF0 : voff,
-                                                        row * rowbytes, dv);
-#else
         // rows the adjoint never re-reads (deferred cherries) stream past the
         // caches (nt), so the re-read rows keep more of L2 / MALL: the
         // 128-tree shard 134 -> 128 us, the full batch unchanged (its table
-        // is ~10x the MALL); TREX_CHERRY_NT=0 builds the uniform policy
-        if (BWD && kAuxCherryRow != kAuxFusedRow && (stp.w & kStepDeferredIn))
-          bst_row<Q, SPT, kAuxCherryRow>(rdp, voff, row * rowbytes, dv);
+        // is ~10x the MALL)
+        if (BWD && (stp.w & kStepDeferredIn))
+          bst_row<Q, kAuxCherryRow>(rdp, voff, row * rowbytes, dv);
         else
-          bst_row<Q, SPT, BWD ? kAuxFusedRow : kAuxFwdRow>(rdp, voff, row * rowbytes, dv);
-#endif
+          bst_row<Q, BWD ? kAuxFusedRow : kAuxFwdRow>(rdp, voff, row * rowbytes, dv);
+        // the row is stored; its one parent takes the message from the table
         if (kPairTables && (stp.w & kStepDeferredIn)) {
-          // the row is stored; its one parent takes the message from the table
 #pragma unroll
-          for (int s = 0; s < SPT; ++s) {
+          for (int s = 0; s < kSites; ++s) {
             float r[Q];
-            lds_vec_get<Q>(tm + pair[s] * Q, r);
+            lds_vec_get<Q>(tm + pair * Q, r);
 #pragma unroll
-            for (int i = 0; i < Q; ++i) dv[i][s] = r[i];
+            for (int i = 0; i < Q; ++i) dv[i] = r[i];
           }
         }
-        if (!(stp.w & kStepToNext) && oslot != 0xFF) {
-          lds_put<Q, SPT>(slots, oslot, lane, dv);
-        }
+        if (!(stp.w & kStepToNext) && oslot != 0xFF) lds_put<Q>(slots, oslot, lane, dv);
 #pragma unroll
         for (int i = 0; i < Q; ++i)
 #pragma unroll
-          for (int s = 0; s < SPT; ++s) prev[i][s] = dv[i][s];
+          for (int s = 0; s < kSites; ++s) prev[i] = dv[i];
       }
     } else {
       // adjoint only: the root row comes from the table
-      bld_row<Q, SPT>(rdp, voff, (n_int - 1) * rowbytes, dv);
+      bld_row<Q>(rdp, voff, (n_int - 1) * rowbytes, dv);
     }
 
     // ---- root: score + cotangent ----
-    float score[SPT], groot[Q][SPT];
-    root_score<Q, SPT, SOFT>(dv, a, bcoef, A.hard_root != 0, score, groot);
+    float score, groot[Q];
+    root_score<Q, SOFT>(dv, a, bcoef, A.hard_root != 0, score, groot);
     if constexpr (FWD) {
       double tot = 0.0;
       if (active) {
 #pragma unroll
-        for (int s = 0; s < SPT; ++s) tot += (double)score[s];
-        if (A.site_score) st<SPT>(A.site_score + site_base + site, score);
+        for (int s = 0; s < kSites; ++s) tot += (double)score;
+        if (A.site_score) A.site_score[site_base + site] = score;
       }
       tot = wave_sum_lane0(tot);
       if (lane == 0) A.part_tree[item] = tot;
@@ -1006,7 +801,7 @@ __device__ __forceinline__ void sankoff_body(const KArgs& A, float* lds) {
 #pragma unroll
       for (int i = 0; i < Q; ++i)
 #pragma unroll
-        for (int s = 0; s < SPT; ++s) groot[i][s] *= f;
+        for (int s = 0; s < kSites; ++s) groot[i] *= f;
 #pragma unroll
       for (int i = 0; i < Q; ++i)
 #pragma unroll
@@ -1014,7 +809,7 @@ __device__ __forceinline__ void sankoff_body(const KArgs& A, float* lds) {
       const bool want_marg = A.marg != nullptr;
       const rsrc_t rmg = make_rsrc(want_marg ? A.marg + rows_base * Q : A.dp, treebytes);
       int8_t* at = A.anc ? A.anc + rows_base + sc : nullptr;
-      lds_put<Q, SPT>(slots, kRootSlot, lane, groot);
+      lds_put<Q>(slots, kRootSlot, lane, groot);
 
       // DP rows of a step's internal children are loaded one step ahead into
       // the other half of a ping-pong buffer (the loop is unrolled by two so
@@ -1023,112 +818,74 @@ __device__ __forceinline__ void sankoff_body(const KArgs& A, float* lds) {
       // unconditional (non-internal children read past the buffer: no
       // memory traffic, zeros) so every path issues the same number of VMEM
       // ops and the compiler's vmcnt waits stay partial.
-      auto prefetch = [&](const I4& s2, float (&nd)[2][Q][SPT]) {
+      auto prefetch = [&](const I4& s2, float (&nd)[2][Q]) {
 #pragma unroll
         for (int c = 0; c < 2; ++c) {
           const int desc = c == 0 ? s2.y : s2.z;
           // deferred cherries (kChildDeferred) are recomputed, not re-read
           const bool internal =
               ((desc >> 24) & 3) == kKindInt && !(desc & kChildDeferred);
-#ifdef TREX_DIAG_NOLOAD
-          const int vo = 0x7FFFFFF0 + 0 * (internal ? voff : 0);
-#else
           const int vo = internal ? voff : 0x7FFFFFF0;
-#endif
           const int crow = internal ? (desc & 0xFFFF) : 0;
-          bld_row<Q, SPT, FWD ? kAuxFusedLoad : kAuxAdjRow>(rdp, vo, crow * rowbytes, nd[c]);
+          bld_row<Q, FWD ? kAuxFusedLoad : kAuxAdjRow>(rdp, vo, crow * rowbytes, nd[c]);
         }
       };
-      float gnext[Q][SPT];  // cotangent handed to the next reverse step (bypass)
-      auto bstep = [&](const I4& stp, float (&cd)[2][Q][SPT]) {
+      float gnext[Q];  // cotangent handed to the next reverse step (bypass)
+      auto bstep = [&](const I4& stp, float (&cd)[2][Q]) {
         if (stp.w & kStepUnreached) return;
         const int row = stp.x & 0xFFFF;
-#ifdef TREX_DIAG_PAD
-        diag_pad(acc[0][0]);
-#endif
-        float g[Q][SPT];
+        float g[Q];
         if (stp.w & kStepToNext) {
 #pragma unroll
-          for (int i = 0; i < Q; ++i)
-#pragma unroll
-            for (int s = 0; s < SPT; ++s) g[i][s] = gnext[i][s];
+          for (int i = 0; i < Q; ++i) g[i] = gnext[i];
         } else {
-          lds_get<Q, SPT>(slots, (stp.w & kStepRoot) ? kRootSlot : ((stp.x >> 16) & 0xFF), lane, g);
+          lds_get<Q>(slots, (stp.w & kStepRoot) ? kRootSlot : ((stp.x >> 16) & 0xFF), lane, g);
         }
-        auto leaf_codes = [&](int desc, int kind, int (&code)[SPT]) {
-          if (kind == kKindLeaf) {
-            child_code(desc, code);
-          } else {
-#pragma unroll
-            for (int s = 0; s < SPT; ++s) code[s] = Q;  // all-1e5 row
-          }
-        };
         if (stp.w & kStepDeferredIn) {
           // g is the parent's cotangent: this step runs the parent -> cherry
           // edge adjoint the parent's step skipped
-          float gc[Q][SPT];
+          float gc[Q];
           if constexpr (PAIR_ADJ) {
             // the edge's u and 1 / s depend on the two leaf codes only
-            int pair[SPT];
+            int pair;
 #pragma unroll
             for (int c = 0; c < 2; ++c) {
               const int desc = c == 0 ? stp.y : stp.z;
-              int code[SPT];
-              leaf_codes(desc, (desc >> 24) & 3, code);
-#pragma unroll
-              for (int s = 0; s < SPT; ++s)
-                pair[s] = c == 0 ? code[s] * (Q + 1) : pair[s] + code[s];
+              const int code = child_code(desc, (desc >> 24) & 3);
+              pair = c == 0 ? code * (Q + 1) : pair + code;
             }
-#pragma unroll
-            for (int s = 0; s < SPT; ++s) {
-              float u[Q], rs[Q], gs[Q], gcs[Q];
-              lds_vec_get<Q>(tu + pair[s] * Q, u);
-              lds_vec_get<Q>(tr + pair[s] * Q, rs);
-#pragma unroll
-              for (int i = 0; i < Q; ++i) gs[i] = g[i][s];
-              softk_edge<Q>(cf, u, rs, gs, acc, gcs);
-#pragma unroll
-              for (int j = 0; j < Q; ++j) gc[j][s] = gcs[j];
-            }
+            float u[Q], rs[Q];
+            lds_vec_get<Q>(tu + pair * Q, u);
+            lds_vec_get<Q>(tr + pair * Q, rs);
+            softk_edge<Q>(cf, u, rs, g, acc, gc);
           } else {
             // the cherry's D is the sum of its two leaf messages (the
             // forward's order, so bit-identical)
-            float dc[Q][SPT];
+            float dc[Q];
 #pragma unroll
             for (int c = 0; c < 2; ++c) {
               const int desc = c == 0 ? stp.y : stp.z;
-              int code[SPT];
-              leaf_codes(desc, (desc >> 24) & 3, code);
+              const int code = child_code(desc, (desc >> 24) & 3);
+              float r[Q];
+              lds_vec_get<Q>(tab + code * Q, r);
 #pragma unroll
-              for (int s = 0; s < SPT; ++s) {
-                float r[Q];
-                lds_vec_get<Q>(tab + code[s] * Q, r);
-#pragma unroll
-                for (int i = 0; i < Q; ++i) dc[i][s] = (c == 0) ? r[i] : dc[i][s] + r[i];
-              }
+              for (int i = 0; i < Q; ++i) dc[i] = (c == 0) ? r[i] : dc[i] + r[i];
             }
-            message_adjoint<Q, SPT, MODE, SYM>(cf, a, dc, g, acc, gc);
+            message_adjoint<Q, MODE, SYM>(cf, a, dc, g, acc, gc);
           }
 #pragma unroll
-          for (int i = 0; i < Q; ++i)
-#pragma unroll
-            for (int s = 0; s < SPT; ++s) g[i][s] = gc[i][s];
+          for (int i = 0; i < Q; ++i) g[i] = gc[i];
         }
         if (want_marg) {
-          bst_row<Q, SPT, kAuxMarg>(rmg, voff, row * rowbytes, g);
+          bst_row<Q, kAuxMarg>(rmg, voff, row * rowbytes, g);
         }
         if (at && active) {
-          int best[SPT];
+          float bv = g[0];
+          int bi = 0;
 #pragma unroll
-          for (int s = 0; s < SPT; ++s) {
-            float bv = g[0][s];
-            int bi = 0;
-#pragma unroll
-            for (int i = 1; i < Q; ++i)
-              if (g[i][s] > bv) { bv = g[i][s]; bi = i; }
-            best[s] = bi;
-          }
-          st_codes<SPT>(at + (size_t)row * Lt, best);
+          for (int i = 1; i < Q; ++i)
+            if (g[i] > bv) { bv = g[i]; bi = i; }
+          st_code(at + (size_t)row * Lt, bi);
         }
 #pragma unroll
         for (int c = 0; c < 2; ++c) {
@@ -1136,47 +893,40 @@ __device__ __forceinline__ void sankoff_body(const KArgs& A, float* lds) {
           const int kind = (desc >> 24) & 3;
           if (kind != kKindInt) {
             // leaf / sentinel child: acc_ij += g_i W[code][i][j] (no cotangent)
-            int code[SPT];
-            leaf_codes(desc, kind, code);
+            const int code = child_code(desc, kind);
 #pragma unroll
-            for (int s = 0; s < SPT; ++s) {
+            for (int s = 0; s < kSites; ++s) {
               float w[Q * Q];
-              lds_vec_get<Q * Q>(tab + kWTab + code[s] * Q * Q, w);
+              lds_vec_get<Q * Q>(tab + kWTab + code * Q * Q, w);
 #pragma unroll
               for (int i = 0; i < Q; ++i) {
                 float wr[Q];
 #pragma unroll
                 for (int j = 0; j < Q; ++j) wr[j] = w[i * Q + j];
-                axpy<Q>(acc[i], g[i][s], wr);
+                axpy<Q>(acc[i], g[i], wr);
               }
             }
           } else {
-            float gc[Q][SPT];
+            float gc[Q];
             if (desc & kChildDeferred) {
               // the child's step runs this edge (kStepDeferredIn)
 #pragma unroll
-              for (int j = 0; j < Q; ++j)
-#pragma unroll
-                for (int s = 0; s < SPT; ++s) gc[j][s] = g[j][s];
+              for (int j = 0; j < Q; ++j) gc[j] = g[j];
             } else {
-              message_adjoint<Q, SPT, MODE, SYM>(cf, a, cd[c], g, acc, gc);
+              message_adjoint<Q, MODE, SYM>(cf, a, cd[c], g, acc, gc);
             }
             if (desc & kChildPrev) {
 #pragma unroll
-              for (int j = 0; j < Q; ++j)
-#pragma unroll
-                for (int s = 0; s < SPT; ++s) gnext[j][s] = gc[j][s];
+              for (int j = 0; j < Q; ++j) gnext[j] = gc[j];
             } else if (kind == kKindInt) {
               const int cslot = (desc >> 16) & 0xFF;
               if (desc & kStepAccumulate) {
-                float old[Q][SPT];
-                lds_get<Q, SPT>(slots, cslot, lane, old);
+                float old[Q];
+                lds_get<Q>(slots, cslot, lane, old);
 #pragma unroll
-                for (int j = 0; j < Q; ++j)
-#pragma unroll
-                  for (int s = 0; s < SPT; ++s) gc[j][s] += old[j][s];
+                for (int j = 0; j < Q; ++j) gc[j] += old[j];
               }
-              lds_put<Q, SPT>(slots, cslot, lane, gc);
+              lds_put<Q>(slots, cslot, lane, gc);
             }
           }
         }
@@ -1186,7 +936,7 @@ __device__ __forceinline__ void sankoff_body(const KArgs& A, float* lds) {
       // earlier (more bytes in flight per wave than a ping-pong; the ring is
       // unrolled so every buffer index is static)
       constexpr int kRing = kAdjRing;
-      float buf[kRing][2][Q][SPT];
+      float buf[kRing][2][Q];
       I4 sd[kRing];
       const I4 none = {0, 0, 0, 0};  // sentinel children only: prefetch reads nothing
 #pragma unroll
@@ -1239,65 +989,57 @@ __device__ __forceinline__ void sankoff_body(const KArgs& A, float* lds) {
   } while (PERSIST && item < item_end);
 }
 
-template <int Q, int SPT, bool SOFT, int PHASE, bool RAGGED = false>
-__global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(PHASE == 1 ? TREX_FWD_WPE : PHASE == 2 ? TREX_ADJ_WPE : TREX_FUSED_WPE, PHASE == 3 ? TREX_FUSED_WPE_MAX : 8)))
+template <int Q, bool SOFT, int PHASE, bool RAGGED = false>
+__global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(
+    PHASE == 1 ? kFwdWpe : PHASE == 2 ? kAdjWpe : kFusedWpe, PHASE == 3 ? kFusedWpeMax : 8)))
 void sankoff_kernel(KArgs A) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   if constexpr (!SOFT) {
-    sankoff_body<Q, SPT, kHard, PHASE, RAGGED>(A, lds);
+    sankoff_body<Q, kHard, PHASE, RAGGED>(A, lds);
   } else {
     float cmin, cmax;
     cost_range<Q>(A.cost, cmin, cmax);
     if (use_ktrick(cmin, cmax, A.a)) {
-#ifndef TREX_NO_KSYM
       // the adjoint-bearing kernels (the forward-only one measured no gain
       // and would carry a third body's scalar registers: 154 -> 245 spilled)
       if ((PHASE & 2) && cost_symmetric<Q>(A.cost))
-        sankoff_body<Q, SPT, kSoftK, PHASE, RAGGED, true>(A, lds);
+        sankoff_body<Q, kSoftK, PHASE, RAGGED, true>(A, lds);
       else
-#endif
-        sankoff_body<Q, SPT, kSoftK, PHASE, RAGGED>(A, lds);
+        sankoff_body<Q, kSoftK, PHASE, RAGGED>(A, lds);
     } else
-      sankoff_body<Q, SPT, kSoftDirect, PHASE, RAGGED>(A, lds);
+      sankoff_body<Q, kSoftDirect, PHASE, RAGGED>(A, lds);
   }
 }
 
 // --------------------------------------------------------------------------
-// trex-exact ancestral reconstruction (sankoff.py:166-185, 191-267)
+// trex-exact ancestral reconstruction (sankoff.py:166-185, 191-267) of a
+// ragged Q <= 4 batch, one lane per site (uniform batches: wide_backtrack).
+// rmeta points at the ragged plan's records; the item table follows them,
+// then the steps and the backtrack entries (see plan.cpp)
 // --------------------------------------------------------------------------
-// RAGGED: bt points at the ragged plan's records (rmeta), the item table
-// follows them, then the steps and the backtrack entries (see plan.cpp)
-template <int Q, int SPT, bool RAGGED = false>
-__global__ __launch_bounds__(kWave) void sankoff_backtrack_kernel(
-    const int2* __restrict__ bt, const float* __restrict__ cost, const float* __restrict__ dp,
-    int n_int, int L, int tiles, int8_t* __restrict__ anc, const int* __restrict__ rmeta = nullptr,
-    int B = 0, int items = 0, int steps = 0) {
-  int tree, tile;
-  size_t rows_base;
-  if constexpr (RAGGED) {
-    const int item = blockIdx.x;
-    tree = as_const(rmeta + (size_t)B * kRaggedMeta)[item];
-    const cptr<int> m = as_const(rmeta) + (size_t)tree * kRaggedMeta;
-    n_int = m[1];
-    L = m[3];
-    tile = item - m[5];
-    rows_base = (size_t)(uint32_t)m[8] | ((size_t)(uint32_t)m[9] << 32);
-    bt = reinterpret_cast<const int2*>(rmeta + (size_t)B * kRaggedMeta + items + (size_t)steps * 4) +
-         m[0];
-  } else {
-    tree = blockIdx.x / tiles;
-    tile = blockIdx.x - tree * tiles;
-    rows_base = (size_t)tree * n_int * L;
-  }
+template <int Q>
+__global__ __launch_bounds__(kWave) void sankoff_ragged_backtrack_kernel(
+    const int* __restrict__ rmeta, const float* __restrict__ cost, const float* __restrict__ dp,
+    int8_t* __restrict__ anc, int B, int items, int steps) {
+  const int item = blockIdx.x;
+  const int tree = as_const(rmeta + (size_t)B * kRaggedMeta)[item];
+  const cptr<int> m = as_const(rmeta) + (size_t)tree * kRaggedMeta;
+  const int n_int = m[1];
+  const int L = m[3];
+  const int tile = item - m[5];
+  const size_t rows_base = (size_t)(uint32_t)m[8] | ((size_t)(uint32_t)m[9] << 32);
+  const int2* bt =
+      reinterpret_cast<const int2*>(rmeta + (size_t)B * kRaggedMeta + items + (size_t)steps * 4) +
+      m[0];
   const int lane = threadIdx.x;
-  const int site = (tile * kWave + lane) * SPT;
+  const int site = tile * kWave + lane;
   if (site >= L) return;
   float c[Q][Q];
 #pragma unroll
   for (int i = 0; i < Q; ++i)
 #pragma unroll
     for (int j = 0; j < Q; ++j) c[i][j] = as_const(cost)[i * Q + j];
-  const cptr<int> prog = as_const(reinterpret_cast<const int*>(bt)) + (RAGGED ? 0 : (size_t)tree * n_int * 2);
+  const cptr<int> prog = as_const(reinterpret_cast<const int*>(bt));
   const size_t rowstride = (size_t)Q * L;  // site-major rows [L][Q]
   const float* dpt = dp + rows_base * Q + (size_t)site * Q;
   int8_t* at = anc + rows_base + site;
@@ -1305,62 +1047,46 @@ __global__ __launch_bounds__(kWave) void sankoff_backtrack_kernel(
     const int2 e = make_int2(prog[2 * k], prog[2 * k + 1]);
     const int x = e.x & 0xFFFF;
     const int kind = (e.x >> 16) & 0xF;
-    int out[SPT];
-    if (kind == kBtUnreached) {
-#pragma unroll
-      for (int s = 0; s < SPT; ++s) out[s] = 0;
-    } else {
-      float d[Q][SPT];
+    int out = 0;
+    if (kind != kBtUnreached) {
+      float d[Q];
       if (kind == kBtSentinel) {
-        fill_sentinel<Q, SPT>(d);
+#pragma unroll
+        for (int j = 0; j < Q; ++j) d[j] = kSentinel;
       } else {
         const float* pr = dpt + (size_t)x * rowstride;
+        if constexpr (Q == 4) {
+          const float4 v = *reinterpret_cast<const float4*>(pr);
+          d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
+        } else {
 #pragma unroll
-        for (int t = 0; t < SPT; ++t) {
-          if constexpr (Q == 4) {
-            const float4 v = reinterpret_cast<const float4*>(pr)[t];
-            d[0][t] = v.x; d[1][t] = v.y; d[2][t] = v.z; d[3][t] = v.w;
-          } else {
-#pragma unroll
-            for (int j = 0; j < Q; ++j) d[j][t] = pr[t * Q + j];
-          }
+          for (int j = 0; j < Q; ++j) d[j] = pr[j];
         }
       }
       if (kind == kBtRoot) {
+        float bv = d[0];
 #pragma unroll
-        for (int s = 0; s < SPT; ++s) {
-          float bv = d[0][s];
-          int bi = 0;
-#pragma unroll
-          for (int j = 1; j < Q; ++j)
-            if (d[j][s] < bv) { bv = d[j][s]; bi = j; }
-          out[s] = bi;
-        }
+        for (int j = 1; j < Q; ++j)
+          if (d[j] < bv) { bv = d[j]; out = j; }
       } else {
-        int sp[SPT];
-        ld_codes<SPT>(at + (size_t)e.y * L, sp);
+        const int sp = ld_code(at + (size_t)e.y * L);  // the parent's state
+        float row[Q];
 #pragma unroll
-        for (int s = 0; s < SPT; ++s) {
-          float row[Q];
+        for (int j = 0; j < Q; ++j) {
+          float v = c[0][j];
 #pragma unroll
-          for (int j = 0; j < Q; ++j) {
-            float v = c[0][j];
+          for (int i = 1; i < Q; ++i) v = (sp == i) ? c[i][j] : v;
+          row[j] = v;
+        }
+        float bv = row[0] + d[0];
 #pragma unroll
-            for (int i = 1; i < Q; ++i) v = (sp[s] == i) ? c[i][j] : v;
-            row[j] = v;
-          }
-          float bv = row[0] + d[0][s];
-          int bi = 0;
-#pragma unroll
-          for (int j = 1; j < Q; ++j) {
-            const float v = row[j] + d[j][s];
-            if (v < bv) { bv = v; bi = j; }
-          }
-          out[s] = bi;
+        for (int j = 1; j < Q; ++j) {
+          const float v = row[j] + d[j];
+          if (v < bv) { bv = v; out = j; }
         }
       }
     }
-    st_codes<SPT>(at + (size_t)x * L, out);
+    st_code(at + (size_t)x * L, out);
   }
 }
 
@@ -1410,11 +1136,11 @@ int check_shape(const char* fn, int B, int L, int n_all, int Q, Shape* sh) {
   return TREX_OK;
 }
 
-int tiles_for(int L, int spt) { return (L + kWave * spt - 1) / (kWave * spt); }
+int tiles_for(int L) { return (L + kWave - 1) / kWave; }
 
-size_t lds_bytes(int n_slots, int nl, int Q, int spt, int phase) {
+size_t lds_bytes(int n_slots, int nl, int Q, int phase) {
   const size_t b = (size_t)tab_floats(phase) * 4 +
-                   (size_t)std::max(n_slots, 1) * Q * kWave * spt * 4 + (size_t)nl * kWave * spt;
+                   (size_t)std::max(n_slots, 1) * Q * kWave * 4 + (size_t)nl * kWave;
   return (b + 15) & ~(size_t)15;
 }
 
@@ -1431,23 +1157,7 @@ int device_cus() {
   return cus;
 }
 
-int hip_check(const char* fn) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return set_error(TREX_E_HIP, "%s: %s", fn, hipGetErrorString(e));
-  return TREX_OK;
-}
-
 int64_t counters_bytes(int B) { return ((int64_t)4 * (B + 1) + 255) / 256 * 256; }
-
-void tau_coefs(float tau, float* a, float* bcoef) {
-  if (tau > 0.0f) {
-    *a = (float)(1.4426950408889634 / (double)tau);
-    *bcoef = (float)((double)tau * 0.6931471805599453);
-  } else {
-    *a = 0.0f;
-    *bcoef = 0.0f;
-  }
-}
 
 // persistent grid: as many single-wave blocks as are co-resident (occupancy
 // x CUs), a multiple of 8 (one share per XCD), never more than the items
@@ -1476,34 +1186,43 @@ int persistent_grid(K kernel, size_t lds, int nitems) {
       if (ncache < 64) cache[ncache++] = Entry{(const void*)kernel, lds, occ};
     }
   }
-#ifdef TREX_FWD_OCC_CAP
-  occ = std::min(occ, TREX_FWD_OCC_CAP);
-#endif
   const long resident = (long)cus * occ / 8 * 8;
   const long want = ((long)nitems + 7) / 8 * 8;
   return (int)std::max(8L, std::min(resident, want));
 }
 
-template <int Q, int SPT, bool SOFT>
+// one site per lane: two doubled the adjoint's VGPRs and were slower at every
+// grid measured
+template <int Q, bool SOFT, bool RAGGED>
 void launch_phase(int phase, size_t lds, hipStream_t st, const KArgs& A) {
   auto go = [&](auto kernel) {
     const int grid = phase == 1 ? persistent_grid(kernel, lds, A.nblocks) : (A.nblocks + 7) / 8 * 8;
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(kWave), lds, st, A);
   };
   if (phase == 1)
-    go(sankoff_kernel<Q, SPT, SOFT, 1>);
+    go(sankoff_kernel<Q, SOFT, 1, RAGGED>);
   else if (phase == 2)
-    go(sankoff_kernel<Q, SPT, SOFT, 2>);
+    go(sankoff_kernel<Q, SOFT, 2, RAGGED>);
   else
-    go(sankoff_kernel<Q, SPT, SOFT, 3>);
+    go(sankoff_kernel<Q, SOFT, 3, RAGGED>);
 }
 
-// one site per lane (SPT = 1): two sites per lane doubled the adjoint's
-// VGPRs and was slower at every grid measured
-template <int Q>
-void dispatch_q(int phase, bool soft, size_t lds, hipStream_t st, const KArgs& A) {
-  if (soft) launch_phase<Q, 1, true>(phase, lds, st, A);
-  else launch_phase<Q, 1, false>(phase, lds, st, A);
+template <bool RAGGED>
+void launch_q(int Q, int phase, bool soft, size_t lds, hipStream_t st, const KArgs& A) {
+  switch (Q) {
+    case 2:
+      if (soft) launch_phase<2, true, RAGGED>(phase, lds, st, A);
+      else launch_phase<2, false, RAGGED>(phase, lds, st, A);
+      break;
+    case 3:
+      if (soft) launch_phase<3, true, RAGGED>(phase, lds, st, A);
+      else launch_phase<3, false, RAGGED>(phase, lds, st, A);
+      break;
+    case 4:
+      if (soft) launch_phase<4, true, RAGGED>(phase, lds, st, A);
+      else launch_phase<4, false, RAGGED>(phase, lds, st, A);
+      break;
+  }
 }
 
 // common entry: validates, fills KArgs, launches one phase
@@ -1552,7 +1271,90 @@ int set_error(int code, const char* fmt, ...) {
   return code;
 }
 
+int hip_check(const char* fn) {
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return set_error(TREX_E_HIP, "%s: %s", fn, hipGetErrorString(e));
+  return TREX_OK;
+}
+
+void tau_coefs(float tau, float* a, float* bcoef) {
+  if (tau > 0.0f) {
+    *a = (float)(1.4426950408889634 / (double)tau);
+    *bcoef = (float)((double)tau * 0.6931471805599453);
+  } else {
+    *a = 0.0f;
+    *bcoef = 0.0f;
+  }
+}
+
 namespace {
+
+// the entry points' arguments as the other kernels' host code takes them; a
+// ragged call passes L = 0 and the largest tree's nl / ni
+WideCall wide_call(int phase, const int* steps, const int8_t* leaves, const float* cost, int B,
+                   int L, int nl, int ni, int Q, int n_slots, float tau, unsigned flags, float* dp,
+                   float* site_score, float* tree_score, const float* dts, float* d_cost,
+                   float* marg, int8_t* anc, void* workspace, void* stream) {
+  WideCall c;
+  c.phase = phase;
+  c.soft = tau > 0.0f;
+  c.steps = steps;
+  c.leaves = leaves;
+  c.cost = cost;
+  c.B = B;
+  c.L = L;
+  c.nl = nl;
+  c.ni = ni;
+  c.Q = Q;
+  c.n_slots = n_slots;
+  tau_coefs(tau, &c.a, &c.bcoef);
+  c.hard_root = (flags & TREX_FLAG_HARD_ROOT) ? 1 : 0;
+  c.dp = dp;
+  c.site_score = site_score;
+  c.tree_score = tree_score;
+  c.dts = dts;
+  c.marg = marg;
+  c.anc = anc;
+  c.d_cost = d_cost;
+  c.workspace = workspace;
+  c.stream = stream;
+  return c;
+}
+
+// the Q <= 4 kernel's arguments of a uniform batch of B trees of n_int rows,
+// L sites and tiles items each, or (n_int = L = tiles = 0; the caller sets
+// rmeta / ritem) of a ragged one; part: the nblocks per-item score partials,
+// then the [Q*Q][nblocks] dC partials
+KArgs kargs(const int* steps, const int8_t* leaves, const float* cost, int n_int, int nl, int L,
+            int tiles, int B, int n_slots, float tau, unsigned flags, float* dp, float* site_score,
+            float* tree_score, const float* dts, float* d_cost, float* marg, int8_t* anc,
+            void* part, int nblocks) {
+  KArgs A;
+  A.steps = reinterpret_cast<const int4*>(steps);
+  A.leaves = leaves;
+  A.cost = cost;
+  A.n_int = n_int;
+  A.nl = nl;
+  A.L = L;
+  A.tiles = tiles;
+  A.B = B;
+  A.n_slots = n_slots;
+  tau_coefs(tau, &A.a, &A.bcoef);
+  A.hard_root = (flags & TREX_FLAG_HARD_ROOT) ? 1 : 0;
+  A.dp = dp;
+  A.site_score = site_score;
+  A.tree_score = tree_score;
+  A.dts = dts;
+  A.marg = marg;
+  A.anc = anc;
+  A.d_cost = d_cost;
+  A.part_tree = static_cast<double*>(part);
+  A.part_dc = A.part_tree + nblocks;
+  A.nblocks = nblocks;
+  A.rmeta = nullptr;
+  A.ritem = nullptr;
+  return A;
+}
 
 int run_phase(const char* fn, int phase, const int32_t* plan, int n_slots, const int8_t* leaves,
               const float* cost, int B, int L, int n_all, int Q, float tau, unsigned flags,
@@ -1580,29 +1382,9 @@ int run_phase(const char* fn, int phase, const int32_t* plan, int n_slots, const
   n_slots &= 0xFFFF;
   if (n_slots > 250) return set_error(TREX_E_ARG, "%s: bad n_slots", fn);
   if (Q > 4 || wide_small_q(B, L, Q)) {
-    WideCall c;
-    c.phase = phase;
-    c.soft = tau > 0.0f;
-    c.steps = plan + TREX_PLAN_HEADER_INTS;
-    c.leaves = leaves;
-    c.cost = cost;
-    c.B = B;
-    c.L = L;
-    c.nl = s.nl;
-    c.ni = s.ni;
-    c.Q = Q;
-    c.n_slots = n_slots;
-    tau_coefs(tau, &c.a, &c.bcoef);
-    c.hard_root = (flags & TREX_FLAG_HARD_ROOT) ? 1 : 0;
-    c.dp = dp;
-    c.site_score = site_score;
-    c.tree_score = tree_score;
-    c.dts = dts;
-    c.marg = marg;
-    c.anc = anc;
-    c.d_cost = d_cost;
-    c.workspace = workspace;
-    c.stream = stream;
+    WideCall c = wide_call(phase, plan + TREX_PLAN_HEADER_INTS, leaves, cost, B, L, s.nl, s.ni, Q,
+                           n_slots, tau, flags, dp, site_score, tree_score, dts, d_cost, marg, anc,
+                           workspace, stream);
     if (Q > kWideMaxQ) return bigq_run(fn, c);  // 64 < Q <= 128 (sankoff_bigq.hip)
     const int32_t* staged = plan + TREX_PLAN_HEADER_INTS + (int64_t)B * s.ni * 6;
     const int32_t* lanes = staged + (int64_t)B * staged_tree_ints(s.ni);
@@ -1636,59 +1418,17 @@ int run_phase(const char* fn, int phase, const int32_t* plan, int n_slots, const
   }
   if ((int64_t)s.ni * L * Q * 4 > 0x7FFFFFF0LL)
     return set_error(TREX_E_UNSUPPORTED, "%s: one tree's DP table exceeds 2 GiB", fn);
-  const int tiles = tiles_for(L, 1);
-  const size_t lds = lds_bytes(n_slots, s.nl, Q, 1, phase);
+  const int tiles = tiles_for(L);
+  const size_t lds = lds_bytes(n_slots, s.nl, Q, phase);
   if (lds > 65536) return set_error(TREX_E_UNSUPPORTED, "%s: LDS stack too deep", fn);
   if ((int64_t)B * tiles > 0x7FFFFFFF) return set_error(TREX_E_ARG, "%s: grid too large", fn);
-  KArgs A;
-  A.rmeta = nullptr;
-  A.ritem = nullptr;
-  A.steps = reinterpret_cast<const int4*>(plan + TREX_PLAN_HEADER_INTS);
-  A.leaves = leaves;
-  A.cost = cost;
-  A.n_int = s.ni;
-  A.nl = s.nl;
-  A.L = L;
-  A.tiles = tiles;
-  A.B = B;
-  A.n_slots = n_slots;
-  tau_coefs(tau, &A.a, &A.bcoef);
-  A.hard_root = (flags & TREX_FLAG_HARD_ROOT) ? 1 : 0;
-  A.dp = dp;
-  A.site_score = site_score;
-  A.tree_score = tree_score;
-  A.dts = dts;
-  A.marg = marg;
-  A.anc = anc;
-  A.d_cost = d_cost;
   // workspace: per-item partials [B*tiles] + [Q*Q][B*tiles] doubles
-  char* w = static_cast<char*>(workspace) + counters_bytes(B);
-  A.part_tree = reinterpret_cast<double*>(w);
-  A.nblocks = B * tiles;
-  A.part_dc = A.part_tree + A.nblocks;
-  const bool soft = tau > 0.0f;
-  hipStream_t st = (hipStream_t)stream;
-  switch (Q) {
-    case 2: dispatch_q<2>(phase, soft, lds, st, A); break;
-    case 3: dispatch_q<3>(phase, soft, lds, st, A); break;
-    case 4: dispatch_q<4>(phase, soft, lds, st, A); break;
-  }
+  const KArgs A = kargs(plan + TREX_PLAN_HEADER_INTS, leaves, cost, s.ni, s.nl, L, tiles, B,
+                        n_slots, tau, flags, dp, site_score, tree_score, dts, d_cost, marg, anc,
+                        static_cast<char*>(workspace) + counters_bytes(B), B * tiles);
+  launch_q<false>(Q, phase, tau > 0.0f, lds, (hipStream_t)stream, A);
   if (int e = hip_check(fn)) return e;
   return partial_reduce(fn, A.part_tree, A.part_dc, B, tiles, Q, phase, tree_score, d_cost, stream);
-}
-
-template <int Q, bool SOFT>
-void launch_ragged(int phase, size_t lds, hipStream_t st, const KArgs& A) {
-  auto go = [&](auto kernel) {
-    const int grid = phase == 1 ? persistent_grid(kernel, lds, A.nblocks) : (A.nblocks + 7) / 8 * 8;
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kWave), lds, st, A);
-  };
-  if (phase == 1)
-    go(sankoff_kernel<Q, 1, SOFT, 1, true>);
-  else if (phase == 2)
-    go(sankoff_kernel<Q, 1, SOFT, 2, true>);
-  else
-    go(sankoff_kernel<Q, 1, SOFT, 3, true>);
 }
 
 }  // namespace
@@ -1714,7 +1454,7 @@ extern "C" int64_t trex_workspace_bytes(int B, int L, int n_all, int Q) {
     const int64_t ni = n_all - (n_all + 1) / 2;
     return site_srow_offset(B, L, Q) + (int64_t)B * std::max<int64_t>(ni, 0) * L * Q * 4;
   }
-  const int64_t nb = (int64_t)B * tiles_for(L, 1);
+  const int64_t nb = (int64_t)B * tiles_for(L);
   const int64_t narrow = counters_bytes(B) + nb * 8 * (1 + (int64_t)Q * Q) + (int64_t)Q * Q * B * 8 + 256;
   // small grids may run the state-parallel wide kernel (G = 4): room for both
   return std::max<int64_t>(narrow, wide_workspace_bytes(B, L, Q));
@@ -1775,8 +1515,8 @@ extern "C" int trex_sankoff_backtrack(const int32_t* plan, int backtrack_ok, con
   const int32_t* bt32 = plan + TREX_PLAN_HEADER_INTS + (int64_t)B * s.ni * 4;
   if (Q > kWideMaxQ) return bigq_backtrack(bt32, cost, dp, B, L, s.ni, Q, anc_states, stream);
   // every uniform batch: the split-lane kernels of sankoff_wide.hip (4 lanes
-  // per site for Q <= 4, 8 for Q <= 32, one lane per site for codons); the
-  // sites-per-lane sankoff_backtrack_kernel serves ragged Q <= 4 batches
+  // per site for Q <= 4, 8 for Q <= 32, one lane per site for codons); ragged
+  // Q <= 4 batches have their own kernel (trex_sankoff_ragged_backtrack)
   return wide_backtrack(bt32, cost, dp, B, L, s.ni, Q, anc_states, stream);
 }
 
@@ -1830,70 +1570,26 @@ extern "C" int trex_sankoff_ragged(int phase, const int32_t* plan, int B, int n_
     return set_error(TREX_E_ARG, "%s: workspace too small", fn);
   if (n_slots < 0 || n_slots > 250) return set_error(TREX_E_ARG, "%s: bad n_slots", fn);
   if (flags & ~TREX_FLAG_HARD_ROOT) return set_error(TREX_E_ARG, "%s: unknown flags 0x%x", fn, flags);
+  // the plan: per-tree records, the work-item -> tree table, the steps
+  const int* meta = plan + TREX_PLAN_HEADER_INTS;
+  const int* ritem = meta + (size_t)B * kRaggedMeta;
+  const int* steps = ritem + items;
   if (Q > 4) {
     // protein / codon alphabets: the state-parallel kernel, each 64-site
     // item split over ceil(64 / sites-per-wave) waves
-    const int* meta = plan + TREX_PLAN_HEADER_INTS;
-    WideCall c;
-    c.phase = phase;
-    c.soft = tau > 0.0f;
-    c.steps = meta + (size_t)B * kRaggedMeta + items;
-    c.leaves = leaves;
-    c.cost = cost;
-    c.B = B;
-    c.L = 0;
-    c.nl = max_nl;
-    c.ni = max_nl - 1;
-    c.Q = Q;
-    c.n_slots = n_slots;
-    tau_coefs(tau, &c.a, &c.bcoef);
-    c.hard_root = (flags & TREX_FLAG_HARD_ROOT) ? 1 : 0;
-    c.dp = dp;
-    c.site_score = site_score;
-    c.tree_score = tree_score;
-    c.dts = d_tree_score;
-    c.marg = marginals;
-    c.anc = anc_states;
-    c.d_cost = d_cost;
-    c.workspace = workspace;
-    c.stream = stream;
-    if (Q > kWideMaxQ) return bigq_ragged_run(fn, c, meta, meta + (size_t)B * kRaggedMeta, items);
-    return wide_ragged_run(fn, c, meta, meta + (size_t)B * kRaggedMeta, items);
+    const WideCall c = wide_call(phase, steps, leaves, cost, B, 0, max_nl, max_nl - 1, Q, n_slots,
+                                 tau, flags, dp, site_score, tree_score, d_tree_score, d_cost,
+                                 marginals, anc_states, workspace, stream);
+    if (Q > kWideMaxQ) return bigq_ragged_run(fn, c, meta, ritem, items);
+    return wide_ragged_run(fn, c, meta, ritem, items);
   }
-  const size_t lds = lds_bytes(n_slots, max_nl, Q, 1, phase);
+  const size_t lds = lds_bytes(n_slots, max_nl, Q, phase);
   if (lds > 65536) return set_error(TREX_E_UNSUPPORTED, "%s: LDS stack too deep", fn);
-  KArgs A;
-  const int* meta = plan + TREX_PLAN_HEADER_INTS;
+  KArgs A = kargs(steps, leaves, cost, 0, max_nl, 0, 0, B, n_slots, tau, flags, dp, site_score,
+                  tree_score, d_tree_score, d_cost, marginals, anc_states, workspace, (int)items);
   A.rmeta = meta;
-  A.ritem = meta + (size_t)B * kRaggedMeta;
-  A.steps = reinterpret_cast<const int4*>(A.ritem + items);
-  A.leaves = leaves;
-  A.cost = cost;
-  A.n_int = 0;
-  A.nl = max_nl;
-  A.L = 0;
-  A.tiles = 0;
-  A.B = B;
-  A.n_slots = n_slots;
-  tau_coefs(tau, &A.a, &A.bcoef);
-  A.hard_root = (flags & TREX_FLAG_HARD_ROOT) ? 1 : 0;
-  A.dp = dp;
-  A.site_score = site_score;
-  A.tree_score = tree_score;
-  A.dts = d_tree_score;
-  A.marg = marginals;
-  A.anc = anc_states;
-  A.d_cost = d_cost;
-  A.nblocks = (int)items;
-  A.part_tree = reinterpret_cast<double*>(workspace);
-  A.part_dc = A.part_tree + items;
-  const bool soft = tau > 0.0f;
-  hipStream_t st = (hipStream_t)stream;
-  switch (Q) {
-    case 2: soft ? launch_ragged<2, true>(phase, lds, st, A) : launch_ragged<2, false>(phase, lds, st, A); break;
-    case 3: soft ? launch_ragged<3, true>(phase, lds, st, A) : launch_ragged<3, false>(phase, lds, st, A); break;
-    case 4: soft ? launch_ragged<4, true>(phase, lds, st, A) : launch_ragged<4, false>(phase, lds, st, A); break;
-  }
+  A.ritem = ritem;
+  launch_q<true>(Q, phase, tau > 0.0f, lds, (hipStream_t)stream, A);
   if (int e = hip_check(fn)) return e;
   return partial_reduce(fn, A.part_tree, A.part_dc, B, 0, Q, phase, tree_score, d_cost, stream,
                         meta + 5, kRaggedMeta, (int)items);
@@ -1918,9 +1614,9 @@ extern "C" int trex_sankoff_ragged_backtrack(const int32_t* plan, int B, int64_t
   if (Q > kWideMaxQ) return bigq_ragged_backtrack(meta, B, items, steps, cost, dp, Q, anc_states, stream);
   if (Q > 4) return wide_ragged_backtrack(meta, B, items, steps, cost, dp, Q, anc_states, stream);
   hipStream_t st = (hipStream_t)stream;
-#define TREX_RBT(QQ)                                                                          \
-  hipLaunchKernelGGL((sankoff_backtrack_kernel<QQ, 1, true>), dim3((int)items), dim3(kWave), 0, \
-                     st, nullptr, cost, dp, 0, 0, 0, anc_states, meta, B, (int)items, (int)steps);
+#define TREX_RBT(QQ)                                                                            \
+  hipLaunchKernelGGL(sankoff_ragged_backtrack_kernel<QQ>, dim3((int)items), dim3(kWave), 0, st, \
+                     meta, cost, dp, anc_states, B, (int)items, (int)steps);
   switch (Q) {
     case 2: TREX_RBT(2) break;
     case 3: TREX_RBT(3) break;

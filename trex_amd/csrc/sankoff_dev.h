@@ -1,5 +1,5 @@
 // Device helpers shared by the Sankoff kernels (sankoff.hip: Q <= 4,
-// sites-per-lane; sankoff_wide.hip: Q > 4, states-per-lane).
+// one site per lane; sankoff_wide.hip: Q > 4, states-per-lane).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -56,6 +56,40 @@ typedef __amdgpu_buffer_rsrc_t rsrc_t;
 
 __device__ __forceinline__ rsrc_t make_rsrc(const void* base, uint32_t bytes) {
   return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);
+}
+
+// Site-major DP rows ([row][L][Q], Q <= 4): a lane's site is Q contiguous
+// floats -> one dwordx4 (Q = 4), dwordx3 or dwordx2 access.  voff = site*Q*4
+// (per lane), soff = row*L*Q*4.  AUX: the buffer instruction's cache-policy
+// bits (2 = nt: a streaming access that should not displace reused lines)
+template <int Q, int AUX = 0>
+__device__ __forceinline__ void bst_row(rsrc_t r, int voff, int soff, const float (&d)[Q]) {
+  if constexpr (Q == 4) {
+    u32x4 w = {__float_as_uint(d[0]), __float_as_uint(d[1]), __float_as_uint(d[2]),
+               __float_as_uint(d[3])};
+    __builtin_amdgcn_raw_buffer_store_b128(w, r, voff, soff, AUX);
+  } else if constexpr (Q == 3) {
+    u32x3 w = {__float_as_uint(d[0]), __float_as_uint(d[1]), __float_as_uint(d[2])};
+    __builtin_amdgcn_raw_buffer_store_b96(w, r, voff, soff, AUX);
+  } else {
+    u32x2 w = {__float_as_uint(d[0]), __float_as_uint(d[1])};
+    __builtin_amdgcn_raw_buffer_store_b64(w, r, voff, soff, AUX);
+  }
+}
+
+template <int Q, int AUX = 0>
+__device__ __forceinline__ void bld_row(rsrc_t r, int voff, int soff, float (&d)[Q]) {
+  if constexpr (Q == 4) {
+    const u32x4 w = __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, AUX);
+    d[0] = __uint_as_float(w.x); d[1] = __uint_as_float(w.y);
+    d[2] = __uint_as_float(w.z); d[3] = __uint_as_float(w.w);
+  } else if constexpr (Q == 3) {
+    const u32x3 w = __builtin_amdgcn_raw_buffer_load_b96(r, voff, soff, AUX);
+    d[0] = __uint_as_float(w.x); d[1] = __uint_as_float(w.y); d[2] = __uint_as_float(w.z);
+  } else {
+    const u32x2 w = __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, AUX);
+    d[0] = __uint_as_float(w.x); d[1] = __uint_as_float(w.y);
+  }
 }
 
 __device__ __forceinline__ double wave_sum(double v) {

@@ -123,18 +123,7 @@ struct Rows {
   }
   __device__ __forceinline__ void get(int row, float (&d)[QP]) const {
     if constexpr (!DYN) {
-      const int vo = site * QP * 4, so = row * L * QP * 4;
-      if constexpr (QP == 4) {
-        const u32x4 w = __builtin_amdgcn_raw_buffer_load_b128(r, vo, so, 0);
-        d[0] = __uint_as_float(w.x); d[1] = __uint_as_float(w.y);
-        d[2] = __uint_as_float(w.z); d[3] = __uint_as_float(w.w);
-      } else if constexpr (QP == 3) {
-        const u32x3 w = __builtin_amdgcn_raw_buffer_load_b96(r, vo, so, 0);
-        d[0] = __uint_as_float(w.x); d[1] = __uint_as_float(w.y); d[2] = __uint_as_float(w.z);
-      } else {
-        const u32x2 w = __builtin_amdgcn_raw_buffer_load_b64(r, vo, so, 0);
-        d[0] = __uint_as_float(w.x); d[1] = __uint_as_float(w.y);
-      }
+      bld_row<QP>(r, site * QP * 4, row * L * QP * 4, d);
     } else {
       const float* p = base + ((size_t)row * L + site) * Q;
 #pragma unroll
@@ -143,18 +132,7 @@ struct Rows {
   }
   __device__ __forceinline__ void put(int row, const float (&d)[QP]) const {
     if constexpr (!DYN) {
-      const int vo = site * QP * 4, so = row * L * QP * 4;
-      if constexpr (QP == 4) {
-        u32x4 w = {__float_as_uint(d[0]), __float_as_uint(d[1]), __float_as_uint(d[2]),
-                   __float_as_uint(d[3])};
-        __builtin_amdgcn_raw_buffer_store_b128(w, r, vo, so, 0);
-      } else if constexpr (QP == 3) {
-        u32x3 w = {__float_as_uint(d[0]), __float_as_uint(d[1]), __float_as_uint(d[2])};
-        __builtin_amdgcn_raw_buffer_store_b96(w, r, vo, so, 0);
-      } else {
-        u32x2 w = {__float_as_uint(d[0]), __float_as_uint(d[1])};
-        __builtin_amdgcn_raw_buffer_store_b64(w, r, vo, so, 0);
-      }
+      bst_row<QP>(r, site * QP * 4, row * L * QP * 4, d);
     } else {
       float* p = const_cast<float*>(base) + ((size_t)row * L + site) * Q;
 #pragma unroll
@@ -279,12 +257,6 @@ __global__ __launch_bounds__(256) void nni_reduce_kernel(const double* __restric
   score[t] = (float)acc;
 }
 
-int nni_hip_check(const char* fn) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return set_error(TREX_E_HIP, "%s: %s", fn, hipGetErrorString(e));
-  return TREX_OK;
-}
-
 int nni_check_shape(const char* fn, int B, int L, int n_all, int Q, float tau) {
   if (B <= 0 || L <= 0 || n_all < 3 || n_all > 65535 || n_all % 2 == 0 || Q < 2)
     return set_error(TREX_E_ARG, "%s: bad shape B=%d L=%d n_all=%d Q=%d", fn, B, L, n_all, Q);
@@ -318,13 +290,7 @@ void nni_fill(NniArgs& A, const int32_t* nni_plan, const int8_t* leaves, const f
   A.ni = n_all - A.nl;
   A.Q = Q;
   A.tiles = (L + kWave - 1) / kWave;
-  if (tau > 0.0f) {
-    A.a = (float)(1.4426950408889634 / (double)tau);
-    A.bcoef = (float)((double)tau * 0.6931471805599453);
-  } else {
-    A.a = 0.0f;
-    A.bcoef = 0.0f;
-  }
+  tau_coefs(tau, &A.a, &A.bcoef);
 }
 
 template <bool SCORE, int QP, bool DYN>
@@ -471,7 +437,7 @@ extern "C" int trex_sankoff_outside(const int32_t* nni_plan, const int8_t* leave
   NniArgs A;
   nni_fill(A, nni_plan, leaves, cost, B, L, n_all, Q, tau, dp, outside);
   nni_launch<false>(tau > 0.0f, (hipStream_t)stream, A);
-  return nni_hip_check(fn);
+  return hip_check(fn);
 }
 
 extern "C" int64_t trex_nni_workspace_bytes(int B, int L, int n_all, int Q) {
@@ -495,12 +461,12 @@ extern "C" int trex_sankoff_nni(const int32_t* nni_plan, const int8_t* leaves, c
   A.part = static_cast<double*>(workspace);
   hipStream_t st = (hipStream_t)stream;
   nni_launch<true>(tau > 0.0f, st, A);
-  if (int e = nni_hip_check(fn)) return e;
+  if (int e = hip_check(fn)) return e;
   const int moves = (A.ni - 1) * 2;
   const int64_t n = (int64_t)B * moves;
   hipLaunchKernelGGL(nni_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
                      A.part, B, A.tiles, moves, nni_score);
-  return nni_hip_check(fn);
+  return hip_check(fn);
 }
 
 extern "C" int64_t trex_attach_workspace_bytes(int B, int L, int n_all, int Q) {
@@ -528,9 +494,9 @@ extern "C" int trex_sankoff_attach(const int32_t* attach_plan, const int8_t* lea
   A.sub_rows = sub_rows;
   hipStream_t st = (hipStream_t)stream;
   attach_launch(tau > 0.0f, st, A);
-  if (int e = nni_hip_check(fn)) return e;
+  if (int e = hip_check(fn)) return e;
   const int64_t n = (int64_t)B * n_all;
   hipLaunchKernelGGL(nni_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
                      A.n.part, B, A.n.tiles, n_all, attach_score);
-  return nni_hip_check(fn);
+  return hip_check(fn);
 }

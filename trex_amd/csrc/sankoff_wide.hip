@@ -124,11 +124,7 @@ __device__ __forceinline__ void wide_body(const WArgs& A, const WCoef<G>& cf_in,
   float* slots = lds + kXchg + wide_tab_floats(G, Q);
   // fused factored softmin: each internal child's stabiliser md per site
   // group, kept from the forward for the adjoint ([n_int][SPW])
-#ifdef TREX_DIAG_NO_KEEPMD
-  constexpr bool KEEP_MD = false;
-#else
   constexpr bool KEEP_MD = PHASE == 3 && MODE == kSoftK && G > 4;
-#endif
   float* mdc = slots + (A.n_slots + 1) * kWave;
   int8_t* lleaf = reinterpret_cast<int8_t*>(mdc + (size_t)(A.nl - 1) * SPW);  // A.nl: max leaves
 

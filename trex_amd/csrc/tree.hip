@@ -28,12 +28,6 @@ namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-int tree_hip_check(const char* fn) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return set_error(TREX_E_HIP, "%s: %s", fn, hipGetErrorString(e));
-  return TREX_OK;
-}
-
 __device__ __forceinline__ double block_sum_256(double v, double* sh) {
   sh[threadIdx.x] = v;
   __syncthreads();
@@ -2243,7 +2237,7 @@ extern "C" int trex_tree_update_seq(const float* x, int n_anc, int L, int Q, flo
   if (rows == 0) return TREX_OK;
   hipLaunchKernelGGL(update_seq_kernel, dim3(grid_for(rows)), dim3(256), 0, (hipStream_t)stream,
                      x, rows, Q, T, s);
-  return tree_hip_check("trex_tree_update_seq");
+  return hip_check("trex_tree_update_seq");
 }
 
 extern "C" int trex_tree_update_seq_bwd(const float* s, const float* ds, int n_anc, int L, int Q,
@@ -2254,7 +2248,7 @@ extern "C" int trex_tree_update_seq_bwd(const float* s, const float* ds, int n_a
   if (rows == 0) return TREX_OK;
   hipLaunchKernelGGL(update_seq_bwd_kernel, dim3(grid_for(rows)), dim3(256), 0,
                      (hipStream_t)stream, s, ds, rows, Q, T, dx);
-  return tree_hip_check("trex_tree_update_seq_bwd");
+  return hip_check("trex_tree_update_seq_bwd");
 }
 
 extern "C" int trex_tree_update_tree(const float* theta, const float* noise, const float* gates,
@@ -2265,11 +2259,11 @@ extern "C" int trex_tree_update_tree(const float* theta, const float* noise, con
   if (n_anc == 0) {  // tree.py:68-69: identity
     hipLaunchKernelGGL(identity_kernel, dim3(grid_for((int64_t)N * N)), dim3(256), 0,
                        (hipStream_t)stream, N, A);
-    return tree_hip_check("trex_tree_update_tree");
+    return hip_check("trex_tree_update_tree");
   }
   hipLaunchKernelGGL(update_tree_kernel, dim3(N), dim3(256), 0, (hipStream_t)stream, theta, noise,
                      gates, N, n_anc, T, A);
-  return tree_hip_check("trex_tree_update_tree");
+  return hip_check("trex_tree_update_tree");
 }
 
 extern "C" int trex_tree_update_tree_bwd(const float* A, const float* dA, const float* gates,
@@ -2278,7 +2272,7 @@ extern "C" int trex_tree_update_tree_bwd(const float* A, const float* dA, const 
     return set_error(TREX_E_ARG, "trex_tree_update_tree_bwd: bad arguments");
   hipLaunchKernelGGL(update_tree_bwd_kernel, dim3(N - 1), dim3(256), 0, (hipStream_t)stream, A,
                      dA, gates, N, n_anc, T, dtheta);
-  return tree_hip_check("trex_tree_update_tree_bwd");
+  return hip_check("trex_tree_update_tree_bwd");
 }
 
 namespace {
@@ -2484,7 +2478,7 @@ int gram(const float* X, const float* Y, int N, int64_t K, int symmetric, float*
     }
     hipLaunchKernelGGL(gram3_reduce_kernel, dim3(p.ntiles * 16), dim3(256), 0, st, part, N, p.ns,
                        p.t0s, p.ntiles, p.ksplit, G);
-    return tree_hip_check("gram");
+    return hip_check("gram");
   }
   if (K % 16 == 0 && x3_max > 0.0f) {
     const float sc = split_scale(x3_max);
@@ -2499,7 +2493,7 @@ int gram(const float* X, const float* Y, int N, int64_t K, int symmetric, float*
   const size_t total = (size_t)g.npairs * 4096;
   hipLaunchKernelGGL(gram_reduce_kernel, dim3(grid_for((int64_t)total)), dim3(256), 0, st, part, N,
                      g.ntile, g.npairs, g.ksplit, symmetric, t0, G);
-  return tree_hip_check("gram");
+  return hip_check("gram");
 }
 }  // namespace
 
@@ -2522,7 +2516,7 @@ extern "C" int trex_tree_surrogate(const float* S, const float* A, int N, int64_
   if (N <= kSurSmallN && (int64_t)N * K <= kSurSmallNK) {
     hipLaunchKernelGGL(surrogate_small_kernel, dim3(1), dim3(1024), 0, st, S, A, N, (int)K, loss,
                        dS, dA, G_out);
-    return tree_hip_check("trex_tree_surrogate");
+    return hip_check("trex_tree_surrogate");
   }
   if (int e = gram(S, S, N, K, 1, G, part, st)) return e;
   hipLaunchKernelGGL(surrogate_combine_kernel, dim3(N), dim3(256), 0, st, A, G, N, dA,
@@ -2539,8 +2533,8 @@ extern "C" int trex_tree_surrogate(const float* S, const float* A, int N, int64_
   if (G_out &&
       hipMemcpyAsync(G_out, G, sizeof(float) * (size_t)N * N, hipMemcpyDeviceToDevice, st) !=
           hipSuccess)
-    return tree_hip_check("trex_tree_surrogate(G)");
-  return tree_hip_check("trex_tree_surrogate");
+    return hip_check("trex_tree_surrogate(G)");
+  return hip_check("trex_tree_surrogate");
 }
 
 extern "C" int trex_tree_soft_cost(const float* S, const float* A, const float* C, int ckind,
@@ -2571,7 +2565,7 @@ extern "C" int trex_tree_soft_cost(const float* S, const float* A, const float* 
   hipLaunchKernelGGL(soft_combine_kernel, dim3(N), dim3(256), 0, st, A, G, N, rowloss);
   hipLaunchKernelGGL(sum_rows_kernel, dim3(1), dim3(256), 0, st, rowloss, N, 1.0f, loss, 0,
                      (const StepState*)nullptr);
-  return tree_hip_check("trex_tree_soft_cost");
+  return hip_check("trex_tree_soft_cost");
 }
 
 extern "C" int trex_tree_constraint(const float* A, int N, float scale, float grad_scale,
@@ -2586,7 +2580,7 @@ extern "C" int trex_tree_constraint(const float* A, int N, float scale, float gr
                      colloss, dA, (const StepState*)nullptr);
   hipLaunchKernelGGL(sum_rows_kernel, dim3(1), dim3(256), 0, st, colloss, n_anc, grad_scale,
                      loss, accumulate, (const StepState*)nullptr);
-  return tree_hip_check("trex_tree_constraint");
+  return hip_check("trex_tree_constraint");
 }
 
 extern "C" int trex_tree_constraint_dev(const float* A, int N, float scale, const void* state,
@@ -2602,7 +2596,7 @@ extern "C" int trex_tree_constraint_dev(const float* A, int N, float scale, cons
                      dA, ss);
   hipLaunchKernelGGL(sum_rows_kernel, dim3(1), dim3(256), 0, st, colloss, n_anc, 0.0f, loss,
                      accumulate, ss);
-  return tree_hip_check("trex_tree_constraint_dev");
+  return hip_check("trex_tree_constraint_dev");
 }
 
 extern "C" int trex_tree_compute_cost(const float* S, const float* A, const float* subst, int N,
@@ -2616,7 +2610,7 @@ extern "C" int trex_tree_compute_cost(const float* S, const float* A, const floa
                      rowcost);
   hipLaunchKernelGGL(sum_rows_kernel, dim3(1), dim3(256), 0, st, rowcost, N - 1, 1.0f, cost, 0,
                      (const StepState*)nullptr);
-  return tree_hip_check("trex_tree_compute_cost");
+  return hip_check("trex_tree_compute_cost");
 }
 
 extern "C" int trex_adam_step(float* params, const float* grads, float* mu, float* nu, int64_t n,
@@ -2630,7 +2624,7 @@ extern "C" int trex_adam_step(float* params, const float* grads, float* mu, floa
   hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, params,
                      grads, mu, nu, n, lr, b1, b2, eps, bc1, bc2, grad_sq_norm_parts, n_parts,
                      clip_norm, (const StepState*)nullptr);
-  return tree_hip_check("trex_adam_step");
+  return hip_check("trex_adam_step");
 }
 
 extern "C" int trex_step_state_bytes(void) { return (int)sizeof(StepState); }
@@ -2641,7 +2635,7 @@ extern "C" int trex_step_advance(void* state, float b1, float b2, const float* t
     return set_error(TREX_E_ARG, "trex_step_advance: bad arguments");
   hipLaunchKernelGGL(step_advance_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream,
                      static_cast<StepState*>(state), b1, b2, temps, n_temps);
-  return tree_hip_check("trex_step_advance");
+  return hip_check("trex_step_advance");
 }
 
 extern "C" int trex_tree_update_tree_bwd_adam(const float* A, const float* dA, const float* gates,
@@ -2657,7 +2651,7 @@ extern "C" int trex_tree_update_tree_bwd_adam(const float* A, const float* dA, c
   hipLaunchKernelGGL(update_tree_bwd_adam_kernel, dim3(N - 1), dim3(256), 0, (hipStream_t)stream,
                      A, dA, gates, N, n_anc, T, dtheta, params, mu, nu, lr, b1, b2, eps, bc1, bc2,
                      static_cast<const StepState*>(state));
-  return tree_hip_check("trex_tree_update_tree_bwd_adam");
+  return hip_check("trex_tree_update_tree_bwd_adam");
 }
 
 extern "C" int trex_adam_step_dev(float* params, const float* grads, float* mu, float* nu,
@@ -2669,7 +2663,7 @@ extern "C" int trex_adam_step_dev(float* params, const float* grads, float* mu, 
   hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, params,
                      grads, mu, nu, n, lr, b1, b2, eps, 1.0f, 1.0f, grad_sq_norm_parts, n_parts,
                      clip_norm, static_cast<const StepState*>(state));
-  return tree_hip_check("trex_adam_step_dev");
+  return hip_check("trex_adam_step_dev");
 }
 
 extern "C" int trex_optax_step(int kind, float* params, const float* grads, float* state1,
@@ -2684,7 +2678,7 @@ extern "C" int trex_optax_step(int kind, float* params, const float* grads, floa
   hipLaunchKernelGGL(optax_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, kind,
                      params, grads, state1, state2, n, lr, b1, b2, eps, weight_decay, bc1, bc2,
                      grad_sq_norm_parts, n_parts, clip_norm, (const StepState*)nullptr);
-  return tree_hip_check("trex_optax_step");
+  return hip_check("trex_optax_step");
 }
 
 extern "C" int trex_optax_step_dev(int kind, float* params, const float* grads, float* state1,
@@ -2698,7 +2692,7 @@ extern "C" int trex_optax_step_dev(int kind, float* params, const float* grads, 
   hipLaunchKernelGGL(optax_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, kind,
                      params, grads, state1, state2, n, lr, b1, b2, eps, weight_decay, 1.0f, 1.0f,
                      grad_sq_norm_parts, n_parts, clip_norm, static_cast<const StepState*>(state));
-  return tree_hip_check("trex_optax_step_dev");
+  return hip_check("trex_optax_step_dev");
 }
 
 extern "C" int trex_adam_seq_step(const float* s_anc, const float* ds_anc, int n_anc, int L,
@@ -2722,7 +2716,7 @@ extern "C" int trex_adam_seq_step(const float* s_anc, const float* ds_anc, int n
   else
     hipLaunchKernelGGL(adam_seq_kernel<0>, dim3(grid_for(rows)), dim3(256), 0, st, s_anc, ds_anc,
                        rows, Q, temperature, params, mu, nu, lr, b1, b2, eps, bc1, bc2, grads_out);
-  return tree_hip_check("trex_adam_seq_step");
+  return hip_check("trex_adam_seq_step");
 }
 
 extern "C" int trex_adam_seq_update_step(const float* ds_anc, int n_anc, int L, int Q,
@@ -2738,7 +2732,7 @@ extern "C" int trex_adam_seq_update_step(const float* ds_anc, int n_anc, int L, 
   const int64_t rows = (int64_t)n_anc * L;
   launch_adam_seq(ds_anc, rows, Q, temperature, next_temperature, params, mu, nu, lr, b1, b2, eps,
                   bc1, bc2, s_next, nullptr, (hipStream_t)stream);
-  return tree_hip_check("trex_adam_seq_update_step");
+  return hip_check("trex_adam_seq_update_step");
 }
 
 extern "C" int trex_adam_seq_update_step_dev(const float* ds_anc, int n_anc, int L, int Q,
@@ -2751,7 +2745,7 @@ extern "C" int trex_adam_seq_update_step_dev(const float* ds_anc, int n_anc, int
   const int64_t rows = (int64_t)n_anc * L;
   launch_adam_seq(ds_anc, rows, Q, 1.0f, 1.0f, params, mu, nu, lr, b1, b2, eps, 1.0f, 1.0f, s_next,
                   static_cast<const StepState*>(state), (hipStream_t)stream);
-  return tree_hip_check("trex_adam_seq_update_step_dev");
+  return hip_check("trex_adam_seq_update_step_dev");
 }
 
 extern "C" int trex_adam_seq_update_step_x3p(const float* ds_anc, int n_anc, int L, int Q,
@@ -2777,7 +2771,7 @@ extern "C" int trex_adam_seq_update_step_x3p(const float* ds_anc, int n_anc, int
                      reinterpret_cast<fv4*>(mu), reinterpret_cast<fv4*>(nu), lr, b1, b2, eps, bc1,
                      bc2, split_scale(max_abs_s), static_cast<fv4*>(s16_next),
                      static_cast<const StepState*>(state));
-  return tree_hip_check("trex_adam_seq_update_step_x3p");
+  return hip_check("trex_adam_seq_update_step_x3p");
 }
 
 extern "C" int trex_sq_norm_parts(const float* x, int64_t n, double* parts, int n_parts,
@@ -2786,7 +2780,7 @@ extern "C" int trex_sq_norm_parts(const float* x, int64_t n, double* parts, int 
     return set_error(TREX_E_ARG, "trex_sq_norm_parts: bad arguments");
   hipLaunchKernelGGL(sq_norm_kernel, dim3(n_parts), dim3(256), 0, (hipStream_t)stream, x, n,
                      parts);
-  return tree_hip_check("trex_sq_norm_parts");
+  return hip_check("trex_sq_norm_parts");
 }
 
 extern "C" int trex_tree_discretize(const float* A, int nrows, int ncols, int n_nodes, float* out,
@@ -2795,7 +2789,7 @@ extern "C" int trex_tree_discretize(const float* A, int nrows, int ncols, int n_
     return set_error(TREX_E_ARG, "trex_tree_discretize: bad arguments");
   hipLaunchKernelGGL(discretize_kernel, dim3(nrows), dim3(256), 0, (hipStream_t)stream, A, ncols,
                      n_nodes, out);
-  return tree_hip_check("trex_tree_discretize");
+  return hip_check("trex_tree_discretize");
 }
 
 // ---- split surrogate phases (for site-sharded multi-GPU: all-reduce G between
@@ -2832,7 +2826,7 @@ extern "C" int trex_tree_gram_mirror(float* G, int N, int row0, void* stream) {
   const int64_t n = (int64_t)row0 * (N - row0);
   hipLaunchKernelGGL(gram_mirror_kernel, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 1024)),
                      dim3(256), 0, (hipStream_t)stream, G, N, row0);
-  return tree_hip_check("trex_tree_gram_mirror");
+  return hip_check("trex_tree_gram_mirror");
 }
 
 extern "C" int trex_tree_gram(const float* S, int N, int64_t K, float* G, void* workspace,
@@ -2859,7 +2853,7 @@ extern "C" int trex_tree_surrogate_constraint(const float* A, const float* G, in
                      colloss, dA, ss);
   hipLaunchKernelGGL(sum_rows2_kernel, dim3(1), dim3(256), 0, st, rowloss, N, colloss, n_anc,
                      grad_scale, loss, ss);
-  return tree_hip_check("trex_tree_surrogate_constraint");
+  return hip_check("trex_tree_surrogate_constraint");
 }
 
 extern "C" int trex_tree_surrogate_combine(const float* A, const float* G, int N, float* loss,
@@ -2872,7 +2866,7 @@ extern "C" int trex_tree_surrogate_combine(const float* A, const float* G, int N
                      rowloss);
   hipLaunchKernelGGL(sum_rows_kernel, dim3(1), dim3(256), 0, st, rowloss, N, 1.0f, loss, 0,
                      (const StepState*)nullptr);
-  return tree_hip_check("trex_tree_surrogate_combine");
+  return hip_check("trex_tree_surrogate_combine");
 }
 
 namespace {
@@ -2898,7 +2892,7 @@ extern "C" int trex_tree_mf_rows(const float* M, const float* S, int N, int64_t 
   const int blocks = nrowt * ((ncolb + 7) / 8 * 8);
   hipLaunchKernelGGL(mf_kernel2<false>, dim3(blocks), dim3(kWave), 0, (hipStream_t)stream, M, S, N,
                      (int)K, row0, nrows, nrowt, ncolb, dS_rows);
-  return tree_hip_check("trex_tree_mf_rows");
+  return hip_check("trex_tree_mf_rows");
 }
 
 namespace {
@@ -2956,7 +2950,7 @@ int mf_x3(const char* fn, const float* M, const float* S, int N, int64_t K, int 
       if (codes) go(mf_kernel3<4, true, true>, 4, lds);
       else go(mf_kernel3<4, false, true>, 4, lds);
     }
-    return tree_hip_check(fn);
+    return hip_check(fn);
   }
   if (v5_ok && (!x3 || (ev && std::atoi(ev) == 5))) {
     // f32: the transposed F slice is CW x 144 B
@@ -2980,7 +2974,7 @@ int mf_x3(const char* fn, const float* M, const float* S, int N, int64_t K, int 
       if (codes) go5(mf_kernel5<4, true, true>, 4);
       else go5(mf_kernel5<4, false, true>, 4);
     }
-    return tree_hip_check(fn);
+    return hip_check(fn);
   }
   if (best == 5) {
     if (codes) go(mf_kernel3<5, true>, 5, lds);
@@ -2989,7 +2983,7 @@ int mf_x3(const char* fn, const float* M, const float* S, int N, int64_t K, int 
     if (codes) go(mf_kernel3<4, true>, 4, lds);
     else go(mf_kernel3<4, false>, 4, lds);
   }
-  return tree_hip_check(fn);
+  return hip_check(fn);
 }
 
 // leaf codes of rows [0, lcr): codesR [lcr][L] bytes, the state of each
@@ -3047,7 +3041,7 @@ extern "C" int trex_tree_leaf_codes(const float* S, int n_leaf, int L, int Q, vo
   const int64_t n = (int64_t)lcr * L;
   hipLaunchKernelGGL(leaf_codes_kernel, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 8192)),
                      dim3(256), 0, st, S, L, lcr, static_cast<uint8_t*>(codes), status);
-  return tree_hip_check("trex_tree_leaf_codes");
+  return hip_check("trex_tree_leaf_codes");
 }
 
 extern "C" int trex_tree_mf_rows_x3_codes(const float* M, const float* S, int N, int64_t K,
@@ -3074,7 +3068,7 @@ extern "C" int trex_tree_split_x3(const float* X, int rows, int cols, int ldx, f
   hipLaunchKernelGGL(split_x3_kernel, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 65536)),
                      dim3(256), 0, (hipStream_t)stream, X, rows, cols, ldx, split_scale(max_abs),
                      static_cast<u32x4*>(out), ldo);
-  return tree_hip_check("trex_tree_split_x3");
+  return hip_check("trex_tree_split_x3");
 }
 
 extern "C" int trex_tree_gram_skip_x3p(const void* S16, int N, int64_t K, int skip_rows,

@@ -65,6 +65,11 @@ constexpr int kBtSentinel = 2;
 constexpr int kBtUnreached = 3;
 
 int set_error(int code, const char* fmt, ...);
+// TREX_OK, or TREX_E_HIP with the pending HIP error's text as the last error
+int hip_check(const char* fn);
+// softmin coefficients of a temperature: a = log2(e) / tau, bcoef = tau ln 2
+// (exp(-x / tau) = exp2(-x a), tau ln(s) = bcoef log2(s)); 0, 0 for tau = 0
+void tau_coefs(float tau, float* a, float* bcoef);
 
 // Host argument checks on the IEEE bit pattern: the library is compiled with
 // -fno-honor-nans (kernels drop NaN canonicalisation), under which the
