@@ -241,13 +241,24 @@ def gram_version(request, monkeypatch):
     return request.param
 
 
-@pytest.mark.parametrize("N,L,r0", [(511, 1001, 256), (300, 257, 0), (64, 5, 0)])
+def _needs_256_cus(device):
+    """The MF picks 5 column tiles per workgroup only when
+    ceil(ceil(K/32)/5) <= CUs < ceil(ceil(K/32)/4): K = 32 800 on 256 CUs."""
+    cus = torch.cuda.get_device_properties(torch.device(device)).multi_processor_count
+    if cus != 256:
+        pytest.skip(f"the TPC = 5 shape is sized for 256 CUs, this device reports {cus}")
+
+
+@pytest.mark.parametrize("N,L,r0", [(511, 1001, 256), (300, 257, 0), (64, 5, 0), (64, 8200, 0)])
 def test_mf_v5_is_bitwise_v3(device, N, L, r0, monkeypatch):
     """MF v5 (one wave per SIMD) keeps v3's per-tile MFMA order (stages,
     then the two k-steps, f16x3 products in the same order): dS bitwise
-    equal, with and without leaf codes."""
+    equal, with and without leaf codes.  L = 8 200 (K = 32 800): the only
+    shape here at 5 column tiles per workgroup (the others take 4)."""
     from trex_amd._lib import check, lib, ptr, stream_handle
 
+    if L == 8200:
+        _needs_256_cus(device)
     S_np, nl = _onehot_case(N, L, N + L)
     K = L * 4
     rng = np.random.default_rng(L)
@@ -295,6 +306,108 @@ def test_gram_x3_stays_inside_its_workspace(device, N, K, skip, gram_version):
     t0 = (skip // 64) * 64
     ref = S64[t0:] @ S64.T
     assert_grad_close(_n(G)[t0:], ref, rtol=1e-5, what="G")  # non-negative sums: per entry
+
+
+@pytest.mark.parametrize("x3", [True, False], ids=["x3", "f32"])
+@pytest.mark.parametrize("N,K,skip", [(64, 208, 0), (224, 208, 0), (256, 208, 0), (288, 208, 0),
+                                      (320, 208, 64), (320, 208, 0), (352, 208, 64),
+                                      (320, 204, 64)])
+def test_gram_every_tile_rung(device, N, K, skip, x3, gram_version):
+    """Every rung of the v5 / v6 Gram's tiles-per-wave ladder
+    (trex_tree_gram_skip_x3 and trex_tree_gram_skip; TREX_GRAM=3 runs the
+    same shapes on v3 / the one-wave-per-tile kernels).  A wave owns T5 tiles
+    and runs the instantiation of the smallest ladder value >= T5 -- {4, 8,
+    10, 12, 13, 16} at 4 waves per workgroup (W = 4), {4, 6, 7, 8} at W = 8
+    (TREX_GRAM=6, x3 only); a wrong rung leaves tiles uncomputed.  With ns =
+    ceil(N / 32) strips, t0s = 2 floor(skip / 64) and ntiles = sum_a (ns -
+    max(a, t0s)), ngroups = ceil(ntiles / 64) and T5 = ceil(ntiles / (W
+    ngroups)):
+
+        (N, skip)   tiles   W = 4: T5 -> rung   W = 8: T5 -> rung
+        (64, 0)       3        1 -> 4              1 -> 4
+        (224, 0)     28        7 -> 8              4 -> 4
+        (256, 0)     36        9 -> 10             5 -> 6
+        (288, 0)     45       12 -> 12             6 -> 6
+        (320, 64)    52       13 -> 13             7 -> 7
+        (320, 0)     55       14 -> 16             7 -> 7
+        (352, 64)    63       16 -> 16             8 -> 8
+
+    K = 208 is 13 whole 16-chunks, K = 204 a ragged last one.  G vs the fp64
+    product per entry outside the skipped block, the skipped block of a
+    pre-filled G untouched, the two halves exactly symmetric."""
+    from trex_amd._lib import check, lib, ptr, stream_handle
+
+    rng = np.random.default_rng(N + K + skip)
+    S = _t(rng.random((N, K)), device)
+    nbytes = int(lib().trex_tree_workspace_bytes(N, K))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    Gm = torch.full((N, N), -7.0, device=device)
+    st = stream_handle(torch.device(device))
+    if x3:
+        check(lib().trex_tree_gram_skip_x3(ptr(S), N, K, skip, 1.0, ptr(Gm), ptr(ws), nbytes, st))
+    else:
+        check(lib().trex_tree_gram_skip(ptr(S), N, K, skip, ptr(Gm), ptr(ws), nbytes, st))
+    torch.cuda.synchronize()
+    t0 = (skip // 64) * 64
+    assert bool(torch.all(Gm[:t0, :t0] == -7.0))
+    mask = np.ones((N, N), bool)
+    mask[:t0, :t0] = False
+    S64 = _n(S)
+    Gn = _n(Gm)
+    assert_grad_close(Gn[mask], (S64 @ S64.T)[mask], rtol=RTOL, what="G")
+    assert torch.equal(Gm, Gm.T)
+
+
+def test_mf_five_column_tiles_f32_vs_fp64(device):
+    """trex_tree_mf_rows (the f32 v5 MF) at 5 column tiles per workgroup
+    (K = 32 800 on 256 CUs, test_mf_v5_is_bitwise_v3's x3 shape) vs fp64."""
+    from trex_amd._lib import check, lib, ptr, stream_handle
+
+    _needs_256_cus(device)
+    N, L = 64, 8200
+    K = L * 4
+    S_np, _ = _onehot_case(N, L, N + L)
+    Mn = np.random.default_rng(L).normal(size=(N, N)) * 20
+    M, S = _t(Mn, device), _t(S_np, device)
+    out = torch.empty((N, K), device=device)
+    check(lib().trex_tree_mf_rows(ptr(M), ptr(S), N, K, 0, N, ptr(out),
+                                  stream_handle(torch.device(device))))
+    M64, S64 = _n(M), S_np.astype(np.float64)
+    assert_bound_close(_n(out), M64 @ S64, RTOL * (np.abs(M64) @ np.abs(S64)), what="dS (f32 MF)")
+
+
+def test_mf_presplit_five_column_tiles_is_bitwise_x3(device):
+    """trex_tree_mf_rows_x3p (pre-split M16 / S16, with and without leaf
+    codes) == trex_tree_mf_rows_x3 bit for bit at 5 column tiles per
+    workgroup (K = 32 800 on 256 CUs): the smallest K at which the pre-split
+    MF takes that width (the optimiser tests above run it at 4)."""
+    from trex_amd._lib import check, lib, ptr, stream_handle
+
+    _needs_256_cus(device)
+    N, L = 64, 8200
+    K = L * 4
+    S_np, nl = _onehot_case(N, L, N + L)
+    M = _t(np.random.default_rng(L).normal(size=(N, N)) * 20, device)
+    S = _t(S_np, device)
+    st = stream_handle(torch.device(device))
+    mx = float(M.abs().max()) * 1.01
+    cb = torch.empty(int(lib().trex_tree_leaf_codes_bytes(nl, L)), dtype=torch.uint8, device=device)
+    status = torch.zeros(1, dtype=torch.int32, device=device)
+    check(lib().trex_tree_leaf_codes(ptr(S), nl, L, 4, ptr(cb), cb.numel(), ptr(status), st))
+    assert int(status.item()) == 0
+    ldm = 64
+    M16 = torch.empty((N, ldm), device=device)
+    S16 = torch.empty_like(S)
+    check(lib().trex_tree_split_x3(ptr(M), N, N, N, mx, ptr(M16), ldm, st))
+    check(lib().trex_tree_split_x3(ptr(S), N, K, K, 1.0, ptr(S16), K, st))
+    ref = torch.empty((N - nl, K), device=device)
+    check(lib().trex_tree_mf_rows_x3(ptr(M), ptr(S), N, K, nl, N - nl, mx, 1.0, ptr(ref), st))
+    for codes in (None, cb):
+        out = torch.empty_like(ref)
+        check(lib().trex_tree_mf_rows_x3p(ptr(M16), ldm, ptr(S16), N, K, nl, N - nl, mx, 1.0,
+                                          ptr(codes), cb.numel() if codes is not None else 0, nl,
+                                          4, ptr(out), st))
+        assert torch.equal(out, ref), "codes" if codes is not None else "plain"
 
 
 @pytest.mark.parametrize("Q", [4, 5])
