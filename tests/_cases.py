@@ -53,6 +53,85 @@ def int_cost(n_states, seed, lo=1, hi=4):
     return c
 
 
+COST_KINDS = ("asym_int", "asym_dyadic", "asym_frac", "neg", "asym_wide")
+
+
+def general_cost(n_states, seed, kind, hi=None):
+    """(Q, Q) float32 cost matrices without the structure of hamming / int_cost
+    (symmetric, zero diagonal, min 0); C[parent][child], every entry drawn on
+    its own, so C != C^T and the diagonal is charged like any other entry.
+
+    "asym_int":    off-diagonal integers 1..hi (5), diagonal 1..2: ties, sums
+                   exact in fp32 (hi = 2: first-index argmin ties everywhere)
+    "asym_dyadic": multiples of 1/8 in [0.25, 2.0]: fractional, still exact
+    "asym_frac":   uniform(0.25, 2.0): softmin only, no ties
+    "neg":         "asym_int" - 7 (entries -6..-2): min(C) < 0
+    "asym_wide":   "asym_int" with off-diagonal 1..10: at tau = 0.05
+                   range(C) / tau > 40, the per-row stabilised softmin
+    """
+    rng = np.random.default_rng(seed)
+    Q = n_states
+    if kind in ("asym_int", "neg", "asym_wide"):
+        top = hi if hi is not None else (10 if kind == "asym_wide" else 5)
+        c = rng.integers(1, top + 1, size=(Q, Q)).astype(np.float32)
+        c[np.arange(Q), np.arange(Q)] = rng.integers(1, 3, size=Q)
+        if kind == "neg":
+            c = c - 7.0
+    elif kind == "asym_dyadic":
+        c = rng.integers(2, 17, size=(Q, Q)).astype(np.float32) / 8.0
+    elif kind == "asym_frac":
+        c = rng.uniform(0.25, 2.0, size=(Q, Q))
+    else:
+        raise ValueError(kind)
+    return c.astype(np.float32)
+
+
+def assert_cost_is_general(cost, ch, leaves, tau, d_tree_score=None, score_condition=True):
+    """A condition on a test's inputs (CPU only, before the GPU is touched):
+    the cost matrix is asymmetric with a non-zero diagonal and a non-zero
+    minimum, and the fp64 oracle tells C from C^T on these trees and leaves --
+    every tree's score differs by more than 1e-3 relative and dC differs from
+    its transpose by more than 1e-2 of its largest entry -- so a kernel that
+    reads C[child][parent], or writes dC transposed, cannot meet the test's
+    bars.  Returns the oracle's result on `cost` (float32 values widened to
+    fp64) for the test to compare against; a case that fails here gets another
+    seed or shape, never a weaker condition.
+
+    A tree's score here is summed over the sites where all its leaves are
+    observed (every site when no code is missing): a missing code is trex's
+    all-1e5 row, which adds ~1e5 to its site's score under C and C^T alike,
+    and a few such sites would put any matrix's difference below 1e-3 of the
+    total.  score_condition=False is for tau = 4 000 only (the general leaf
+    tables): there C / tau ~ 1e-3 and the score is tau log-sum terms that no
+    matrix of these kinds moves by 1e-3 (measured 2e-7 .. 3e-6 over seeds
+    1 .. 29), so the orientation is pinned by the dC condition alone, which
+    the elementwise dC bar then enforces."""
+    from oracle.softmin_ref import batched_fwd_bwd_ref
+
+    cost = np.asarray(cost)
+    leaves = np.asarray(leaves)
+    assert cost.dtype == np.float32 and cost.ndim == 2 and cost.shape[0] == cost.shape[1]
+    assert (cost != cost.T).any(), "cost is symmetric"
+    assert (np.diag(cost) != 0).all(), "cost has a zero on its diagonal"
+    assert cost.min() != 0, "min(cost) is 0"
+    c64 = cost.astype(np.float64)
+    ref = batched_fwd_bwd_ref(ch, leaves, c64, tau, d_tree_score=d_tree_score)
+    ref_t = batched_fwd_bwd_ref(ch, leaves, np.ascontiguousarray(c64.T), tau,
+                                d_tree_score=d_tree_score)
+    seen = ((leaves >= 0) & (leaves < cost.shape[0])).all(axis=1)  # (B, L)
+    assert seen.any(axis=1).all(), "a tree has no site with every leaf observed"
+    ts, ts_t = (ref["site_score"] * seen).sum(axis=1), (ref_t["site_score"] * seen).sum(axis=1)
+    rel = np.abs(ts - ts_t) / np.abs(ts)
+    if score_condition:
+        assert (rel > 1e-3).all(), f"tree scores under C and C^T: rel diff {rel} (need > 1e-3 each)"
+    else:
+        assert tau >= 1000.0
+    dc = ref["d_cost"]
+    asym = np.abs(dc - dc.T).max() / np.abs(dc).max()
+    assert asym > 1e-2, f"|dC - dC^T|.max() / |dC|.max() = {asym:.3e} (need > 1e-2)"
+    return ref
+
+
 def random_leaves(B, n_leaves, L, n_states, seed, missing=0.0):
     rng = np.random.default_rng(seed)
     x = rng.integers(0, n_states, size=(B, n_leaves, L)).astype(np.int8)
@@ -351,7 +430,8 @@ def landscape_grad_bound(ancestors, masked_sequences, n_leaves, interactions, fi
     return rtol * temperature * softmax_vjp_bound(pa, mag[n_leaves:])
 
 
-__all__ = ["simulate_leaves", "hamming", "int_cost", "random_leaves", "balanced_children",
+__all__ = ["simulate_leaves", "hamming", "int_cost", "COST_KINDS", "general_cost",
+           "assert_cost_is_general", "random_leaves", "balanced_children",
            "weird_children", "random_topologies", "create_balanced_binary_tree",
            "assert_grad_close", "cond_rtol", "assert_bound_close", "assert_dp_close", "path_dmax", "marginal_rtol",
            "assert_marginals_close", "clear_argmax_mask", "surrogate_grad_bounds", "softmax_vjp_bound",

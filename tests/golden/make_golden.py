@@ -41,6 +41,29 @@ KAT = {
     # d total / d cost (tie-averaged, hard): root argmin state 0 at both
     # sites; every message picks a unique argmin; see DESIGN.md "KAT".
     "d_cost": [[6, 2], [0, 0]],
+    # the same fixture under an asymmetric matrix, C[parent][child]
+    # (sankoff.py:67-68, min(cost_matrix + dp[child], axis=1)), by hand:
+    # node 3 = (0, 1): D3[i] = C[i][0] + C[i][1] = [3, 4] at both sites (the
+    # leaves are 0, 1 and 1, 0); node 4 = (2, 3), leaf 2 = 0: D4[i] = C[i][0]
+    # + min_j (C[i][j] + D3[j]) = [1 + min(4, 6), 4 + min(7, 4)] = [5, 8];
+    # total 2 * 5; root 0, node 3 argmin_j (C[0][j] + D3[j]) = 0; per site the
+    # edges charge C[0][0] three times (leaf 2, node 3, leaf 0 | 1) and
+    # C[0][1] once.  Under C^T: D3 = [5, 2], D4 = [1 + 6, 2 + 2] = [7, 4],
+    # total 8, root and node 3 in state 1.
+    "asymmetric": {
+        "cost": [[1, 2], [4, 0]],
+        "total": 10.0,
+        "dp": [[[0, 1e5], [1e5, 0], [0, 1e5], [3, 4], [5, 8]],
+               [[1e5, 0], [0, 1e5], [0, 1e5], [3, 4], [5, 8]]],
+        "reconstructed": [[0, 1], [1, 0], [0, 0], [0, 0], [0, 0]],
+        "d_cost": [[6, 2], [0, 0]],
+        "transposed": {
+            "total": 8.0,
+            "dp": [[[0, 1e5], [1e5, 0], [0, 1e5], [5, 2], [7, 4]],
+                   [[1e5, 0], [0, 1e5], [0, 1e5], [5, 2], [7, 4]]],
+            "reconstructed": [[0, 1], [1, 0], [0, 0], [1, 1], [1, 1]],
+        },
+    },
     "run_dp_fixture": {
         "source": "reference tests/test_sankoff.py:9-36",
         "adjacency": [[0, 1, 0], [0, 1, 0], [0, 0, 0]],

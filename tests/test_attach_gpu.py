@@ -14,7 +14,8 @@ import torch
 
 import _attach_ref as A
 import _nni_ref as R
-from _cases import hamming, int_cost, random_leaves, random_topologies, simulate_leaves
+from _cases import (assert_cost_is_general, cond_rtol, general_cost, hamming, int_cost,
+                    random_leaves, random_topologies, simulate_leaves)
 from test_nni_gpu import SHAPES, case as nni_case
 from trex_amd import (SankoffEngine, TreePlan, TrexError, insert_leaf, nni_hill_climb,
                       parsimony_search, stepwise_addition)
@@ -24,13 +25,16 @@ pytestmark = pytest.mark.gpu
 
 
 @functools.lru_cache(maxsize=None)
-def case(n, L, Q, tau):
-    """test_nni_gpu's inputs (B = 3 topologies, missing codes at n = 6, the
-    asymmetric cost at n = 9), the new leaf = row n of random_leaves(3, n + 1),
-    and the fp64 references; computed once per case, read-only."""
-    ch, lv, cost, _ = nni_case(n, L, Q, tau)
+def case(n, L, Q, tau, missing=None):
+    """test_nni_gpu's inputs (B = 3 topologies, missing codes at n = 6,
+    asymmetric costs with a non-zero diagonal in every case), the new leaf =
+    row n of random_leaves(3, n + 1), and the fp64 references; computed once
+    per case, read-only."""
+    ch, lv, cost, _ = nni_case(n, L, Q, tau, missing)
     hard = tau == 0.0
-    new = random_leaves(3, n + 1, L, Q, seed=n + L, missing=0.05 if (hard and n == 6) else 0.0)
+    if missing is None:
+        missing = 0.05 if (hard and n == 6) else 0.0
+    new = random_leaves(3, n + 1, L, Q, seed=n + L, missing=missing)
     new = np.ascontiguousarray(new[:, n])
     ref = np.stack([A.attach_ref(ch[b], lv[b], cost, tau, new_codes=new[b]) for b in range(3)])
     bf = np.stack([A.brute_force(ch[b], np.concatenate([lv[b], new[b][None]]), cost, tau)
@@ -90,27 +94,40 @@ def test_one_hot_sub_rows_give_the_bits_of_new_leaf(device):
         assert torch.equal(got, sc)
 
 
+SUBTREE_CASES = [(4, 0.0, 44), (5, 0.0, 1), (4, 0.5, 44), (5, 0.5, 44)]  # Q, tau, cost seed
+
+
 def test_a_whole_subtree_through_sub_rows(device):
     """Tree S (3 leaves) attached on every edge of tree A (6 leaves): the
-    regraft half of an SPR move.  Integer costs, tau = 0: exact."""
-    L, Q = 70, 4
+    regraft half of an SPR move.  Asymmetric costs; Q = 4 and Q = 5 (the
+    padded kernel's sub_rows read); tau = 0 with integer costs: exact,
+    tau = 0.5: within 1e-5 of the fp64 forward on the grafted trees."""
+    L = 70
     cha = random_topologies(1, 6, seed=41)
     chs = random_topologies(1, 3, seed=42)
-    lv = random_leaves(1, 9, L, Q, seed=43)  # disjoint rows: A 0..5, S 6..8
-    cost = int_cost(Q, seed=44)
-    cd = torch.from_numpy(cost).to(device)
-    lva = torch.from_numpy(lv[:, :6]).to(device).contiguous()
-    lvs = torch.from_numpy(lv[:, 6:]).to(device).contiguous()
-    rows = SankoffEngine(TreePlan(chs), L, Q, device).forward(lvs, cd, 0.0).dp[:, -1].contiguous()
-    assert rows.shape == (1, L, Q)
-    sc = SankoffEngine(TreePlan(cha), L, Q, device).attach_scores(lva, cd, 0.0, sub_rows=rows)
-    want = np.array([R.sankoff_fwd_bwd_ref(A.graft_ref(cha[0], chs[0], x), lv[0], cost,
-                                           0.0)["tree_score"] for x in range(11)])
-    assert want.max() < 2 ** 24 and len(np.unique(want)) > 3
-    assert torch.equal(sc.cpu()[0], torch.from_numpy(want.astype(np.float32)))
+    for Q, tau, seed in SUBTREE_CASES:
+        lv = random_leaves(1, 9, L, Q, seed=43)  # disjoint rows: A 0..5, S 6..8
+        cost = general_cost(Q, seed, "asym_int" if tau == 0.0 else "asym_frac")
+        assert_cost_is_general(cost, cha, lv[:, :6], tau)
+        cd = torch.from_numpy(cost).to(device)
+        lva = torch.from_numpy(lv[:, :6]).to(device).contiguous()
+        lvs = torch.from_numpy(lv[:, 6:]).to(device).contiguous()
+        rows = SankoffEngine(TreePlan(chs), L, Q, device).forward(lvs, cd, tau).dp[:, -1].contiguous()
+        assert rows.shape == (1, L, Q)
+        sc = SankoffEngine(TreePlan(cha), L, Q, device).attach_scores(lva, cd, tau, sub_rows=rows)
+        want = np.array([R.sankoff_fwd_bwd_ref(A.graft_ref(cha[0], chs[0], x), lv[0], cost,
+                                               tau)["tree_score"] for x in range(11)])
+        assert len(np.unique(want)) > 3
+        if tau == 0.0:
+            assert want.max() < 2 ** 24
+            assert torch.equal(sc.cpu()[0], torch.from_numpy(want.astype(np.float32))), (Q, tau)
+        else:
+            rel = np.abs(sc.cpu().numpy()[0].astype(np.float64) - want) / np.abs(want)
+            print(f"subtree through sub_rows Q={Q} tau={tau}: worst rel err {rel.max():.3e}")
+            assert rel.max() <= 1e-5, (Q, tau, rel.max())
 
 
-@pytest.mark.parametrize("n,L,Q", [(6, 70, 4), (9, 129, 4), (8, 65, 20)])
+@pytest.mark.parametrize("n,L,Q", SHAPES)  # Q = 2, 3; Q = 5: the padded soft kernel, dead states
 def test_softmin_within_1e5_of_fp64_brute_force(device, n, L, Q):
     tau = 0.5
     ch, lv, cost, new, ref, bf = case(n, L, Q, tau)
@@ -119,6 +136,24 @@ def test_softmin_within_1e5_of_fp64_brute_force(device, n, L, Q):
     rel = np.abs(got - bf) / np.abs(bf)
     print(f"attach softmin n={n} L={L} Q={Q}: worst rel err {rel.max():.3e}")
     assert rel.max() <= 1e-5, f"attachment scores: worst rel err {rel.max():.3e}"
+
+
+def test_softmin_with_missing_codes(device):
+    """5 % missing codes (the new leaf's too) under the softmin: the bar is
+    max(1e-5, cond_rtol) -- fp32 D carries trex's 1e5 offsets -- and the fp64
+    outside-table reference alone meets it against the fp64 brute force."""
+    n, L, Q, tau = 6, 70, 4, 0.5
+    ch, lv, cost, new, ref, bf = case(n, L, Q, tau, 0.05)
+    assert (lv < 0).any() and (new < 0).any()
+    dmax = max(float(np.abs(r["inside"]).max()) for r in nni_case(n, L, Q, tau, 0.05)[3])
+    bar = max(1e-5, cond_rtol(np.array([dmax]), tau))
+    rel_ref = np.abs(ref - bf) / np.abs(bf)
+    assert rel_ref.max() <= bar, f"fp64 reference vs brute force: {rel_ref.max():.3e} > {bar:.3e}"
+    eng, lvd, cd, nd, f, out, sc = run(device, ch, lv, cost, new, tau)
+    rel = np.abs(sc.cpu().numpy().astype(np.float64) - bf) / np.abs(bf)
+    print(f"attach softmin with missing codes: fp64 reference {rel_ref.max():.3e}, device "
+          f"{rel.max():.3e}, bar {bar:.3e}")
+    assert rel.max() <= bar, f"attachment scores: worst rel err {rel.max():.3e} > {bar:.3e}"
 
 
 @pytest.mark.parametrize("tau", [0.0, 0.5])

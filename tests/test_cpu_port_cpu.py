@@ -12,8 +12,8 @@ from __future__ import annotations
 import numpy as np
 import pytest
 
-from _cases import (assert_grad_close, hamming, int_cost, random_leaves, random_topologies,
-                    weird_children)
+from _cases import (assert_cost_is_general, assert_grad_close, general_cost, hamming, int_cost,
+                    random_leaves, random_topologies, weird_children)
 from oracle import cpu_port
 from oracle.softmin_ref import batched_fwd_bwd_ref
 
@@ -59,6 +59,30 @@ def test_cpu_port_f32_baseline_tracks_oracle(tau):
     cost = hamming(4)
     ref = batched_fwd_bwd_ref(ch, lv, cost, tau)
     ts, dc, _ = cpu_port.fwd_bwd(ch, lv, cost, tau, precision="f32")
+    if tau == 0.0:
+        assert np.array_equal(ts, ref["tree_score"])
+        np.testing.assert_allclose(dc, ref["d_cost"], rtol=1e-6)
+    else:
+        np.testing.assert_allclose(ts, ref["tree_score"], rtol=1e-5)
+        assert_grad_close(dc, ref["d_cost"], rtol=1e-4)
+
+
+@pytest.mark.parametrize("kind,tau,Q,seed", [("asym_frac", 0.5, 4, 1), ("neg", 0.0, 4, 1),
+                                             ("neg", 0.5, 20, 2), ("asym_frac", 0.1, 20, 1)])
+def test_cpu_port_general_cost(kind, tau, Q, seed):
+    """Asymmetric matrices with a non-zero diagonal and min(C) != 0
+    (tests/_cases.py general_cost; the guard shows that the oracle tells C
+    from C^T on these inputs): the fp64 port and the fp32 baseline at the
+    bars of the two tests above."""
+    ch, lv = _case("random", Q)
+    cost = general_cost(Q, seed, kind)
+    tau32 = float(np.float32(tau))
+    ref = assert_cost_is_general(cost, ch, lv, tau32)
+    ts, dc, dp = cpu_port.fwd_bwd(ch, lv, cost, tau32, want_dp=True, precision="f64")
+    np.testing.assert_allclose(ts, ref["tree_score"], rtol=1e-11)
+    assert_grad_close(dc, ref["d_cost"], rtol=1e-11)
+    np.testing.assert_allclose(dp, ref["dp"].astype(np.float32), rtol=1e-6, atol=1e-9)
+    ts, dc, _ = cpu_port.fwd_bwd(ch, lv, cost, tau32, precision="f32")
     if tau == 0.0:
         assert np.array_equal(ts, ref["tree_score"])
         np.testing.assert_allclose(dc, ref["d_cost"], rtol=1e-6)

@@ -12,8 +12,8 @@ import pytest
 import torch
 
 import _nni_ref as R
-from _cases import (balanced_children, hamming, int_cost, random_leaves, random_topologies,
-                    simulate_leaves)
+from _cases import (assert_cost_is_general, balanced_children, cond_rtol, general_cost, hamming,
+                    int_cost, random_leaves, random_topologies, simulate_leaves)
 from trex_amd import SankoffEngine, TreePlan, TrexError, apply_nni, nni_hill_climb
 from trex_amd._lib import TREX_E_UNSUPPORTED
 
@@ -34,9 +34,14 @@ SHAPES = [(3, 1, 2), (4, 63, 3), (6, 70, 4), (9, 129, 4), (7, 33, 5), (8, 65, 20
 
 
 @functools.lru_cache(maxsize=None)
-def case(n, L, Q, tau):
+def case(n, L, Q, tau, missing=None):
     """Inputs (B = 3, a different topology per tree) and the fp64 references,
-    computed once per case and shared (treated as read-only)."""
+    computed once per case and shared (treated as read-only).  Costs are
+    asymmetric with a non-zero diagonal (tests/_cases.py general_cost):
+    integers for the hard cases, so their scores stay exact, uniform(0.25, 2)
+    for the softmin ones; the oracle tells C from C^T on every case
+    (assert_cost_is_general), so the DYN path's p[i * Q + j] and the TRANS
+    messages cannot be read the other way round unnoticed."""
     ch = random_topologies(3, n, seed=10 * n + Q)
     if n == 8:
         ch[0] = balanced_children(8)[0]
@@ -44,10 +49,12 @@ def case(n, L, Q, tau):
     if n == 9:
         ch[1] = caterpillar(9)
     hard = tau == 0.0
-    lv = random_leaves(3, n, L, Q, seed=n + L, missing=0.05 if (hard and n == 6) else 0.0)
-    cost = int_cost(Q, seed=Q) if (hard or Q == 20) else hamming(Q)
-    if hard and n == 9:  # asymmetric integer costs
-        cost = cost + np.triu(np.ones_like(cost), 1) * 2
+    if missing is None:
+        missing = 0.05 if (hard and n == 6) else 0.0
+    lv = random_leaves(3, n, L, Q, seed=n + L, missing=missing)
+    kind = "asym_int" if hard else "asym_frac"
+    cost = general_cost(Q, Q, kind)
+    assert_cost_is_general(cost, ch, lv, tau)
     ref = [R.nni_ref(ch[b], lv[b], cost, tau) for b in range(3)]
     return ch, lv, cost.astype(np.float32), ref
 
@@ -101,7 +108,9 @@ def test_hard_mode_equals_engine_forward_on_rebuilt_trees(device):
     assert len(torch.unique(nni)) > 10  # the moves do change the score
 
 
-@pytest.mark.parametrize("n,L,Q", [(6, 70, 4), (9, 129, 4), (8, 65, 20)])
+# every instantiation: Q = 2, 3 (nni_*_kernel<2 | 3, false, true>), 4, the padded
+# soft kernel with dead states (Q = 5: live(j) keeps them out of the exp-sum) and Q = 20
+@pytest.mark.parametrize("n,L,Q", SHAPES)
 def test_softmin_within_1e5_of_fp64_brute_force(device, n, L, Q):
     tau = 0.5
     ch, lv, cost, ref = case(n, L, Q, tau)
@@ -120,6 +129,26 @@ def test_softmin_within_1e5_of_fp64_brute_force(device, n, L, Q):
     ref_ts = np.array([r["tree_score"] for r in ref])
     rel_ts = np.abs(inv - ref_ts[:, None]) / np.abs(ref_ts[:, None])
     assert rel_ts.max() <= 1e-5, f"invariant vs fp64: worst rel err {rel_ts.max():.3e}"
+
+
+def test_softmin_with_missing_codes(device):
+    """5 % missing codes under the softmin: every D carries trex's 1e5
+    offsets, so the bar is max(1e-5, cond_rtol) as in the wide kernels'
+    missing-leaf tests; the fp64 outside-table reference alone meets it
+    against the fp64 brute force, then the device does."""
+    n, L, Q, tau = 6, 70, 4, 0.5
+    ch, lv, cost, ref = case(n, L, Q, tau, 0.05)
+    assert (lv < 0).any()
+    bf = np.stack([R.brute_force(ch[b], lv[b], cost, tau) for b in range(3)])
+    dmax = max(float(np.abs(r["inside"]).max()) for r in ref)
+    bar = max(1e-5, cond_rtol(np.array([dmax]), tau))
+    rel_ref = np.abs(np.stack([r["nni"] for r in ref]) - bf) / np.abs(bf)
+    assert rel_ref.max() <= bar, f"fp64 reference vs brute force: {rel_ref.max():.3e} > {bar:.3e}"
+    eng, lvd, cd, f, out, nni = run(device, ch, lv, cost, tau)
+    rel = np.abs(nni.cpu().numpy().astype(np.float64) - bf) / np.abs(bf)
+    print(f"nni softmin with missing codes: fp64 reference {rel_ref.max():.3e}, device "
+          f"{rel.max():.3e}, bar {bar:.3e}")
+    assert rel.max() <= bar, f"neighbour scores: worst rel err {rel.max():.3e} > {bar:.3e}"
 
 
 @pytest.mark.parametrize("tau", [0.0, 0.5])

@@ -39,6 +39,34 @@ def test_kat_run_sankoff():
     np.testing.assert_array_equal(o["d_cost"], np.array(k["d_cost"]))
 
 
+def test_kat_asymmetric_cost_orientation():
+    """The orientation the oracle is trusted for, C[parent][child]
+    (sankoff.py:67-68): the reference's 3-leaf fixture under C = [[1, 2],
+    [4, 0]], hand-derived (tests/golden/make_golden.py), and under C^T, which
+    gives another total and other ancestors."""
+    k = _kat()
+    adj = np.zeros((5, 5))
+    for c, p in k["adjacency_edges"]:
+        adj[c, p] = 1
+    seqs = np.array(k["leaf_sequences"], dtype=np.float32)
+    a = k["asymmetric"]
+    cost = np.array(a["cost"], dtype=np.float32)
+    assert a["cost"] == [[1, 2], [4, 0]]
+    for c, want in ((cost, a), (cost.T.copy(), a["transposed"])):
+        recon, dp, total = run_sankoff_ref(adj, c, seqs, 5, 2, 3, return_path=True)
+        assert total == np.float32(want["total"])
+        np.testing.assert_array_equal(dp, np.array(want["dp"], dtype=np.float32))
+        np.testing.assert_array_equal(recon, np.array(want["reconstructed"], dtype=np.float32))
+        o = sankoff_fwd_bwd_ref(trex_children_table(adj), normalize_leaves(seqs, 2), c, 0.0)
+        assert o["tree_score"] == want["total"]
+        np.testing.assert_array_equal(o["dp"][:, :, 0], np.array(want["dp"])[0, 3:])
+        if "d_cost" in want:
+            np.testing.assert_array_equal(o["d_cost"], np.array(want["d_cost"]))
+    assert a["total"] == 10.0 and a["transposed"]["total"] == 8.0
+    assert np.array(a["reconstructed"])[3:].max() == 0
+    assert np.array(a["transposed"]["reconstructed"])[3:].min() == 1
+
+
 def test_kat_run_dp_fixture():
     k = _kat()["run_dp_fixture"]
     adj = np.array(k["adjacency"], dtype=np.float32)

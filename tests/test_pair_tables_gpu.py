@@ -13,8 +13,8 @@ import numpy as np
 import pytest
 import torch
 
-from _cases import (assert_dp_close, assert_grad_close, balanced_children, cond_rtol, int_cost,
-                    random_leaves, random_topologies, weird_children)
+from _cases import (assert_dp_close, assert_grad_close, balanced_children, cond_rtol, general_cost,
+                    int_cost, random_leaves, random_topologies, weird_children)
 from oracle.softmin_ref import batched_fwd_bwd_ref
 from trex_amd import SankoffEngine, TreePlan
 from trex_amd.ragged import RaggedSankoffEngine, RaggedTreePlan
@@ -113,10 +113,30 @@ def _run_all(eng, lv, c, tau, dts):
     return f, dc, mg, an
 
 
-@pytest.mark.parametrize("mode", list(MODES))
+def _cost(Q, mode, cost_kind):
+    """"sym": the symmetric zero-diagonal integer matrix; "asym_int": every
+    entry on its own, diagonal 1..2 (a cherry of two equal codes i under
+    state i costs 2 C[i][i] != 0; C[i][a] and C[a][i] differ), with the wide
+    range ("asym_wide") for the direct mode.  The every-ordered-code-pair
+    leaf layout is what tells C[i][a] from C[a][i] in the tables; the sites
+    with missing codes put 1e5 offsets into the tree score, so the score
+    condition of assert_cost_is_general is not asked of these inputs."""
+    if cost_kind == "sym":
+        return int_cost(Q, seed=COST_SEED, hi=MODES[mode][1])
+    cost = general_cost(Q, 1, "asym_wide" if mode == "direct" else "asym_int")
+    assert (cost != cost.T).any() and (np.diag(cost) != 0).all() and cost.min() != 0
+    return cost
+
+
+# the symmetric cases keep their ids; "-asym_int" marks the new ones
+MODE_KINDS = ([pytest.param(m, "sym", id=m) for m in MODES]
+              + [pytest.param(m, "asym_int", id=f"{m}-asym_int") for m in MODES])
+
+
+@pytest.mark.parametrize("mode,cost_kind", MODE_KINDS)
 @pytest.mark.parametrize("tree", ["balanced", "fwdref", "dag"])
 @pytest.mark.parametrize("Q", [2, 3, 4])
-def test_every_code_pair_every_mode(device, monkeypatch, Q, tree, mode):
+def test_every_code_pair_every_mode(device, monkeypatch, Q, tree, mode, cost_kind):
     """Every ordered pair of leaf codes (missing included, as -1 and as 127)
     under a cherry, in the hard, factored, direct and general-leaf-table
     modes, on trees with four deferred cherries ("balanced"), with a cherry
@@ -129,11 +149,11 @@ def test_every_code_pair_every_mode(device, monkeypatch, Q, tree, mode):
     and states (dC: summation order only); DP, tree score and dC meet the
     fp64 oracle's bounds, tau = 4 000 included (the parent commit passes the
     same comparison)."""
-    tau, hi = MODES[mode]
+    tau, _ = MODES[mode]
     L = 70
     ch = _tree(tree)
     leaves = _pair_leaves(ch, L, Q, seed=10 * Q + 1)
-    cost = int_cost(Q, seed=COST_SEED, hi=hi)
+    cost = _cost(Q, mode, cost_kind)
     if mode == "direct":
         assert (cost.max() - cost.min()) / tau > 40.0
     seen = set()

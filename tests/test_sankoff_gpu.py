@@ -84,6 +84,32 @@ def test_run_sankoff_reference_fixture_kat(device):
     assert torch.all(recon[:3] == torch.as_tensor(seqs[:3], device=device))
 
 
+def test_run_sankoff_reference_fixture_asymmetric_kat(device):
+    """The same fixture under C = [[1, 2], [4, 0]], C[parent][child]
+    (sankoff.py:67-68), hand-derived in tests/golden/make_golden.py: total 10,
+    ancestors 0, dC = [[6, 2], [0, 0]]; under C^T total 8 and ancestors 1."""
+    import json
+    import os
+
+    with open(os.path.join(os.path.dirname(__file__), "golden", "kat_sankoff.json")) as fh:
+        k = json.load(fh)
+    adj = np.zeros((5, 5), dtype=np.int32)
+    for child, parent in k["adjacency_edges"]:
+        adj[child, parent] = 1
+    seqs = np.array(k["leaf_sequences"], dtype=np.float32)
+    a = k["asymmetric"]
+    cost = np.array(a["cost"], np.float32)
+    for c, want in ((cost, a), (cost.T.copy(), a["transposed"])):
+        recon, dp, total = run_sankoff(adj, c, seqs, 5, 2, 3, return_path=True, device=device)
+        assert float(total) == want["total"]
+        np.testing.assert_array_equal(dp.cpu().numpy(), np.array(want["dp"], np.float32))
+        np.testing.assert_array_equal(recon.cpu().numpy(),
+                                      np.array(want["reconstructed"], np.float32))
+    total, dc = sankoff_value_and_grad(adj, cost, seqs, 5, 2, 3, device=device)
+    assert float(total) == a["total"]
+    np.testing.assert_array_equal(dc.cpu().numpy(), np.array(a["d_cost"], np.float32))
+
+
 def test_convergence_setup_invariant(device):
     """tests/test_convergence.py:42-73: Sankoff total == compute_cost(onehot(recon))."""
     seqs, adj = simulate_leaves(4, 20, 4, 3, seed=42)
