@@ -375,3 +375,77 @@ def test_site_kernel_smaller_workspace_recomputes_s_rows_bitwise(device):
             eng.fwd_bwd(lv, c, tau)
     finally:
         eng.workspace = full
+
+
+def _deep33_children():
+    """33 leaves: eight 4-leaf caterpillars (the smallest height-3 task rows)
+    joined pairwise, plus one leaf at the root -- 12 lane-program slots, the
+    most whose LDS the 8-pair wave-pair kernel still fits (161 040 of 163 840
+    bytes; the one-wave kernel 147 920)."""
+    n = 33
+    ch = np.full((2 * n - 1, 2), -1, np.int32)
+    nxt = n
+
+    def node(a, b):
+        nonlocal nxt
+        ch[nxt] = (a, b)
+        nxt += 1
+        return nxt - 1
+
+    level = [node(node(node(4 * k, 4 * k + 1), 4 * k + 2), 4 * k + 3) for k in range(8)]
+    while len(level) > 1:
+        level = [node(level[i], level[i + 1]) for i in range(0, len(level), 2)]
+    node(level[0], n - 1)
+    return ch[None]
+
+
+_LDS_CASES = {}
+
+
+def _lds_case(Q, L, deep):
+    """Shared, read-only: topology, leaves, cost and the fp64 oracle of one case."""
+    key = (Q, L, deep)
+    if key not in _LDS_CASES:
+        B = 2
+        ch = np.repeat(_deep33_children(), B, axis=0) if deep else balanced_children(8, B)
+        n = (ch.shape[1] + 1) // 2
+        leaves = random_leaves(B, n, L, Q, seed=7 * Q + L + n, missing=0.03)
+        cost = int_cost(Q, seed=5)  # range 3 <= 40 tau: the gate takes it
+        _LDS_CASES[key] = (ch, leaves, cost, batched_fwd_bwd_ref(ch, leaves, cost, 1.0))
+    return _LDS_CASES[key]
+
+
+@pytest.mark.parametrize("L", [70, 72])  # byte / dword leaf staging; a partial second tile
+@pytest.mark.parametrize("Q", [20, 13])
+def test_site_kernels_deep_tree_after_shallow_one(device, monkeypatch, Q, L):
+    """One instantiation of the lane-per-site kernel (and, under
+    TREX_SITE2=8, of the wave-pair kernel) runs a shallow tree and then, in
+    the same process, a deep one that needs more dynamic LDS (1 -> 12
+    lane-program slots, 8 -> 33 leaves): the launcher's dynamic-LDS ceiling,
+    set once per instantiation, must not be the first call's size.  Fused
+    call, tau = 1, against the fp64 oracle at the suite's softmin bars."""
+    from trex_amd._lib import lib
+
+    tau = 1.0
+    for pairs in (None, "8"):
+        if pairs is None:
+            monkeypatch.delenv("TREX_SITE2", raising=False)
+        else:
+            monkeypatch.setenv("TREX_SITE2", pairs)
+        slots = []
+        for deep in (False, True):
+            ch, leaves, cost, ref = _lds_case(Q, L, deep)
+            eng = _engine(ch, L, Q, device)
+            slots.append(eng.plan.lane_slots)
+            n0 = lib().trex_debug_site2_launches()
+            f, dc, _, _ = eng.fwd_bwd(_dev(leaves, device), _dev(cost, device, torch.float32), tau,
+                                      site_score=True)
+            torch.cuda.synchronize()
+            assert lib().trex_debug_site2_launches() - n0 == (1 if pairs else 0), (pairs, deep)
+            np.testing.assert_allclose(f.tree_score.cpu().numpy(), ref["tree_score"],
+                                       rtol=SOFT_RTOL)
+            np.testing.assert_allclose(f.site_score.cpu().numpy(), ref["site_score"],
+                                       rtol=SOFT_RTOL, atol=1e-5)
+            assert_dp_close(_sm(f.dp), ref, SOFT_RTOL)
+            assert_grad_close(dc.cpu().numpy(), ref["d_cost"], rtol=cond_rtol(ref["dp"], tau))
+        assert slots == [1, 12]

@@ -4,12 +4,13 @@ between translation units:
 
     make -C trex_amd/csrc tree.s                      # in a worktree of the old commit
     make -C trex_amd/csrc tree.s tree_gram.s ...      # in the new tree
-    tools/asm_kernels.py OLD.s [OLD.s ...] -- NEW.s [NEW.s ...]
+    tools/asm_kernels.py [--rename=A=B ...] OLD.s [OLD.s ...] -- NEW.s [NEW.s ...]
 
 Each side's `make NAME.s` listings are cut into one chunk per function, keyed
 by the demangled name, and the kernels' metadata entries likewise; a chunk is
 normalised (c++filt; `.section` / `.file` / `.ident` / comment lines dropped;
-`__hip_cuid_<hash>` collapsed; the function's ordinal taken out of `.LBB<n>_`
+`__hip_cuid_<hash>` collapsed; each `--rename`'s demangled text A replaced by B,
+for a type the change renamed; the function's ordinal taken out of `.LBB<n>_`
 and `.Lfunc_end<n>` labels, which count functions per file) and the two sides
 compared by name: instructions, labels, `.amdhsa_*` and metadata.  Prints the
 names that differ or exist on one side only; exit status 1 if any."""
@@ -18,9 +19,14 @@ import subprocess
 import sys
 
 
+RENAMES = []
+
+
 def chunks(path):
     with open(path) as f:
         raw = subprocess.run(["c++filt"], stdin=f, capture_output=True, text=True, check=True).stdout
+    for a, b in RENAMES:
+        raw = raw.replace(a, b)
     raw = re.sub(r"__hip_cuid_[0-9a-f]+", "__hip_cuid", raw)
     text, _, meta = raw.partition("\t.amdgpu_metadata")
     text = text.split("\t.set amdgpu.max_num_vgpr")[0]  # the file's trailer
@@ -56,6 +62,8 @@ def side(paths):
 
 def main():
     args = sys.argv[1:]
+    while args[0].startswith("--rename="):
+        RENAMES.append(tuple(args.pop(0)[len("--rename="):].split("=", 1)))
     sep = args.index("--")
     (of, om), (nf, nm) = side(args[:sep]), side(args[sep + 1:])
     print(f"old: {len(of)} functions, {len(om)} kernels; new: {len(nf)} functions, {len(nm)} kernels")

@@ -1144,8 +1144,6 @@ size_t lds_bytes(int n_slots, int nl, int Q, int phase) {
   return (b + 15) & ~(size_t)15;
 }
 
-constexpr size_t kLdsPerCu = 160 * 1024;
-
 int device_cus() {
   static const int cus = [] {
     int dev = 0, n = 0;

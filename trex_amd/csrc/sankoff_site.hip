@@ -20,9 +20,10 @@
 // uses the same K, so it costs no VGPRs and no LDS bandwidth.  The one
 // cross-site reduction, dC = sum over sites and children of r u^T (x K), runs
 // on the matrix core: per child the wave writes r and u to its LDS scratch,
-// reads them back transposed and issues 32 v_mfma_f32_32x32x2_f32 (k = two
-// sites each); leaf children add g e_code^T into a second accumulator the
-// same way (the one-hot columns built from the leaf codes).
+// reads them back transposed, splits each exactly into three bf16 pieces and
+// issues 24 v_mfma_f32_32x32x16_bf16 (k = 16 sites each); leaf children add
+// g e_code^T into a second accumulator the same way (the one-hot columns
+// built from the leaf codes).
 //
 // The tree runs as the height-levelled task program of plan.cpp
 // (lane_program_one_tree): rows of height <= 2 are recomputed inline by the
@@ -35,101 +36,29 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cmath>
-#include <cstdlib>
 
-#include "sankoff_dev.h"
-#include "trex_common.h"
-#include "wide_dev.h"
+#include "site_dev.h"
 
 namespace trex {
-
-#ifndef TREX_SITE_LOAD_AUX
-#define TREX_SITE_LOAD_AUX 1  // cache policy of the adjoint's DP-row re-reads (1 = sc0)
-#endif
 namespace {
-constexpr int kSiteLoadAux = TREX_SITE_LOAD_AUX;
-
-constexpr int kSQ = kSiteSQ;               // states per lane (Q padded to 20)
-constexpr int kSWv = 8;                    // waves per workgroup
-constexpr int kSlotF = kSQ * kWave;        // floats per slot / scratch vector
-constexpr int kTabF = (kSQ + 1) * kSQ + kSQ;  // leaf messages T[Q + 1][kSQ] + 1 / sum_j K_ij
-
-typedef float f16v __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-#ifndef SITE_DC_BF16
-#define SITE_DC_BF16 1  // 0: the dC outer products on f32 32x32x2 MFMAs (A/B, PERFLOG)
-#endif
-
-// eight floats (two float4 at p0, p1) split exactly into truncated bf16
-// pieces x = h + m + l, packed two per dword in k order
-__device__ __forceinline__ void split3(const float* p0, const float* p1, u32x4& h, u32x4& m, u32x4& l) {
-  const float4 a = *reinterpret_cast<const float4*>(p0), b = *reinterpret_cast<const float4*>(p1);
-  const float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    // the two residual subtractions of a pair as one v_pk_add_f32 each
-    typedef unsigned int u2 __attribute__((ext_vector_type(2)));
-    const f2 x = pk(v[2 * q], v[2 * q + 1]);
-    const u2 xb = __builtin_bit_cast(u2, x);
-    const f2 r1 = x - __builtin_bit_cast(f2, xb & 0xFFFF0000u);
-    const u2 mb = __builtin_bit_cast(u2, r1) & 0xFFFF0000u;
-    const u2 lb = __builtin_bit_cast(u2, r1 - __builtin_bit_cast(f2, mb));
-    // high halves of (e0, e1) -> one dword, e0 in the low half
-    h[q] = __builtin_amdgcn_perm(xb.y, xb.x, 0x07060302u);
-    m[q] = __builtin_amdgcn_perm(mb.y, mb.x, 0x07060302u);
-    l[q] = __builtin_amdgcn_perm(lb.y, lb.x, 0x07060302u);
-  }
-}
+// cache policy of the adjoint's DP-row re-reads: sc0 (nt / sc0 nt: C3 107-108 vs 99-100 us, PERFLOG r06)
+constexpr int kSiteLoadAux = 1;
+constexpr int kSWv = 8;  // waves per workgroup
 
 __device__ __forceinline__ f16v mfma_bf(const u32x4& a, const u32x4& b, const f16v& c) {
   return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0,
                                                  0, 0);
 }
 
-struct SiteArgs {
-  const int* lanes;  // lane programs (trex_common.h)
-  int64_t stride;    // ints per tree region
-  const int8_t* leaves;
-  const float* cost;
-  int n_int, nl, L, tiles, B, Q;
-  float a, bcoef;
-  int hard_root;
-  float* dp;          // [B][n_int][L][Q]
-  float* site_score;  // [B][L] or null
-  const float* dts;   // [B] or null
-  float* marg;        // [B][n_int][L][Q] or null
-  int8_t* anc;        // [B][n_int][L] or null
-  double* part_tree;  // [B * tiles]
-  double* part_dc;    // [Q * Q][B * tiles]
-  const float* kg;    // K [kSQ][kSQ] and K^T (site_gate_write), zero-padded
-  const float* ptab;  // cherry tables TM | TS (site_pair_tables), below K
-  int cherry;         // 0: the CH = false variants (TREX_SITE_CHERRY=0, A/B; bitwise the same)
-  float* srow;        // fused: s = K u of each computed internal child row, [B][n_int][L][Q]
-  const int* flag;    // 1: this kernel handles the launch
-  int n_slots;
-};
-
 #ifdef TREX_SITE_TIMING
-// diagnostic build (tools/build_ab.sh sitet sankoff_site.hip -DTREX_SITE_TIMING):
-// lane 0 of every wave of the first 2048 workgroups stamps s_memtime at phase
-// boundaries (tools/site_times.py)
+// tools/build_ab.sh sitet sankoff_site.hip -DTREX_SITE_TIMING (tools/site_times.py)
 __device__ unsigned long long g_site_t[2048][8][20];
-#define SITE_STAMP(j)                                                              \
-  do {                                                                             \
-    if ((threadIdx.x & 63) == 0 && blockIdx.x < 2048 && (j) < 20)                  \
-      g_site_t[blockIdx.x][threadIdx.x >> 6][j] = __builtin_amdgcn_s_memtime();   \
-  } while (0)
+#define SITE_STAMP(j) SITE_STAMP_TO(g_site_t, j)
 #else
 #define SITE_STAMP(j) \
   do {                \
   } while (0)
 #endif
-
-__device__ __forceinline__ void site_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
 
 // scratch swizzle: row i of a [kSQ][64] scratch keeps site s at s ^ 4 (i & 15)
 // (4-site groups stay contiguous; 16 rows read at one site group hit 16
@@ -173,14 +102,10 @@ __global__ __launch_bounds__(kSWv * kWave, 1) void sankoff_site_kernel(SiteArgs 
   // loops stay rolled (an unrolled product would hoist all Q^2 loads into
   // SGPRs), their per-row results go through the wave's scratch column
 
-  float cmin;
-  {
-    float lmin = INFINITY;
-    for (int e = lane; e < Q * Q; e += kWave) lmin = fminf(lmin, A.cost[e]);
-    cmin = uniform(wave_minf(lmin));
-  }
+  const float cmin = site_cost_min(A.cost, Q, lane);
   // leaf message table: T[code][i] = C[i][code] (exact: the 1e5 sentinel
-  // dominates), T[Q][i] = the all-1e5 row's message, sinv[i] = 1 / sum_j K_ij
+  // dominates), T[Q][i] = the all-1e5 row's message
+  // (this loop and the staging below are sankoff_site2.hip's too, spelled out in both: shared, they changed this kernel's code)
   for (int e = threadIdx.x; e < (kSQ + 1) * kSQ; e += kSWv * kWave) {
     const int code = e / kSQ, i = e - code * kSQ;
     float v = 0.0f;
@@ -195,12 +120,7 @@ __global__ __launch_bounds__(kSWv * kWave, 1) void sankoff_site_kernel(SiteArgs 
     }
     tab[e] = v;
   }
-  if (threadIdx.x < kSQ) {
-    const int i = threadIdx.x;
-    float sk = 0.0f;
-    for (int j = 0; j < Q; ++j) sk += A.kg[i * kSQ + j];
-    sinv[i] = i < Q ? __builtin_amdgcn_rcpf(sk) : 0.0f;
-  }
+  site_row_sum_inv(A.kg, Q, sinv);
   // the tree's program into LDS (one coalesced pass instead of dependent
   // scalar misses on the step chain) and the tile's leaf codes (dwords of 4
   // sites when rows are 4-byte aligned), all loads in flight together
@@ -263,9 +183,6 @@ __global__ __launch_bounds__(kSWv * kWave, 1) void sankoff_site_kernel(SiteArgs 
   const int tb = tile * kWave * Q * 4;  // this tile's first byte in a row
   const int tbytes = (min(L, (tile + 1) * kWave) - tile * kWave) * Q * 4;
   auto store_row = [&](rsrc_t r, int row, const float (&v)[kSQ]) {
-#ifdef SITE_DIAG_NOSTORE  // diagnostic: no row stores (wrong results)
-    return;
-#endif
     if (q4) {
 #pragma unroll
       for (int c = 0; c < kSQ / 4; ++c)
@@ -331,7 +248,7 @@ __global__ __launch_bounds__(kSWv * kWave, 1) void sankoff_site_kernel(SiteArgs 
         if (j < Q) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v[j]), r, vbase + 4 * j, row * rowbytes, 0);
     }
   };
-  auto load_row_direct = [&](rsrc_t rr, int row, float (&v)[kSQ]) {
+  auto load_row_r = [&](rsrc_t rr, int row, float (&v)[kSQ]) {
     if (q4) {
 #pragma unroll
       for (int c = 0; c < kSQ / 4; ++c) {
@@ -349,57 +266,7 @@ __global__ __launch_bounds__(kSWv * kWave, 1) void sankoff_site_kernel(SiteArgs 
                      : 0.0f;
     }
   };
-  auto load_row_t = [&](rsrc_t rr, int row, float (&v)[kSQ]) {
-    if (q4) {
-#pragma unroll
-      for (int c = 0; c < kSQ / 4; ++c) {
-        if (4 * c < Q) {
-          const int o = 16 * (lane + kWave * c);
-          const u32x4 w = __builtin_amdgcn_raw_buffer_load_b128(rr, o < tbytes ? tb + o : 0x7FFFFFF0,
-                                                               row * rowbytes, kSiteLoadAux);
-          *reinterpret_cast<u32x4*>(reinterpret_cast<char*>(xr) + o) = w;
-        }
-      }
-      lds_sync();
-#pragma unroll
-      for (int c = 0; c < kSQ / 4; ++c) {
-        float4 w = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        if (4 * c < Q) w = *reinterpret_cast<const float4*>(xr + lane * Q + 4 * c);
-        v[4 * c] = w.x;
-        v[4 * c + 1] = w.y;
-        v[4 * c + 2] = w.z;
-        v[4 * c + 3] = w.w;
-      }
-    } else {
-#pragma unroll
-      for (int j = 0; j < kSQ; ++j) {
-        if (j < Q) {
-          const int o = 4 * (lane + kWave * j);
-          xr[lane + kWave * j] = __uint_as_float(
-              __builtin_amdgcn_raw_buffer_load_b32(rr, o < tbytes ? tb + o : 0x7FFFFFF0, row * rowbytes, kSiteLoadAux));
-        }
-      }
-      lds_sync();
-#pragma unroll
-      for (int j = 0; j < kSQ; ++j) v[j] = j < Q ? xr[lane * Q + j] : 0.0f;
-    }
-    lds_sync();
-  };
-#ifndef SITE_LOAD_T
-#define SITE_LOAD_T 0  // transposed (synchronous) row loads: slower in the adjoint (PERFLOG)
-#endif
-  auto load_row_r = [&](rsrc_t rr, int row, float (&v)[kSQ]) {
-    if (SITE_LOAD_T)
-      load_row_t(rr, row, v);
-    else
-      load_row_direct(rr, row, v);
-  };
   auto load_row = [&](int row, float (&v)[kSQ]) { load_row_r(rdp, row, v); };
-#ifdef SITE_DIAG_HOTROW  // diagnostic: the adjoint's row loads all read row 0 (cache-hot; wrong math)
-#define SITE_ADJ_ROW(x) 0
-#else
-#define SITE_ADJ_ROW(x) (x)
-#endif
   auto slot_get = [&](int sl, float (&v)[kSQ]) {
 #pragma unroll
     for (int j = 0; j < kSQ; ++j) v[j] = slots[(size_t)sl * kSlotF + j * kWave + lane];
@@ -465,11 +332,7 @@ __global__ __launch_bounds__(kSWv * kWave, 1) void sankoff_site_kernel(SiteArgs 
     const cptr<float> KT = K + kSQ * kSQ;
 #pragma unroll 2
     for (int j = 0; j < Q; ++j) {
-#ifdef SITE_DIAG_NOSMEM  // diagnostic: one K column for every j (loads hoisted; wrong math)
-      const cptr<float> kc = KT;
-#else
       const cptr<float> kc = KT + j * kSQ;
-#endif
       const float uj = xu[j * kWave + lane];
 #pragma unroll
       for (int i = 0; i < kSQ; i += 2) s2[i / 2] = __builtin_elementwise_fma(pk(kc[i], kc[i + 1]), pk(uj, uj), s2[i / 2]);
@@ -673,11 +536,6 @@ __global__ __launch_bounds__(kSWv * kWave, 1) void sankoff_site_kernel(SiteArgs 
     // acc1 += r u^T over the wave's 64 sites (MFMA k = 2 sites)
     // acc1 += (scratch r)(scratch u)^T, the scratch already written
     auto outer_mfma = [&]() {
-#ifdef SITE_DIAG_NOMFMA  // diagnostic: no dC outer products (wrong dC)
-      wave_sync();
-      return;
-#endif
-#if SITE_DC_BF16
       // r and u split exactly into three truncated 8-bit pieces each (hi + mid
       // + lo); the six products down to 2^-16 of |r u| (hl, lh, mm, mh, hm, hh,
       // smallest first) on v_mfma_f32_32x32x16_bf16, k = 16 sites: dropped
@@ -696,18 +554,6 @@ __global__ __launch_bounds__(kSWv * kWave, 1) void sankoff_site_kernel(SiteArgs 
         acc1 = mfma_bf(ah, bm, acc1);
         acc1 = mfma_bf(ah, bh, acc1);
       }
-#else
-#pragma unroll
-      for (int t4 = 0; t4 < 8; ++t4) {
-        const int sg = khalf * 32 + 4 * t4;
-        const float4 ra = *reinterpret_cast<const float4*>(xr + swz(rrow, sg));
-        const float4 ub = *reinterpret_cast<const float4*>(xu + swz(rrow, sg));
-        acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(ra.x, ub.x, acc1, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(ra.y, ub.y, acc1, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(ra.z, ub.z, acc1, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(ra.w, ub.w, acc1, 0, 0, 0);
-      }
-#endif
       wave_sync();
     };
     auto outer = [&](const float (&r)[kSQ], const float (&u)[kSQ]) {
@@ -725,9 +571,6 @@ __global__ __launch_bounds__(kSWv * kWave, 1) void sankoff_site_kernel(SiteArgs 
     // sites per v_mfma_f32_32x32x16_bf16 (12 per 64 sites instead of 32
     // 32x32x2 f32 MFMAs)
     auto leaf_hist = [&](const float (&g)[kSQ], int d0, int d1) {
-#ifdef SITE_DIAG_NOMFMA
-      return;
-#endif
 #pragma unroll
       for (int i = 0; i < kSQ; ++i) xr[swz(i, lane)] = g[i];
       wave_sync();
@@ -778,11 +621,7 @@ __global__ __launch_bounds__(kSWv * kWave, 1) void sankoff_site_kernel(SiteArgs 
       for (int j = 0; j < kSQ / 2; ++j) t2[j] = pk(0.0f, 0.0f);
 #pragma unroll 2
       for (int i = 0; i < Q; ++i) {
-#ifdef SITE_DIAG_NOSMEM
-        const cptr<float> kr = K;
-#else
         const cptr<float> kr = K + i * kSQ;
-#endif
         const float ri = xr[swz(i, lane)];
 #pragma unroll
         for (int j = 0; j < kSQ; j += 2)
@@ -825,16 +664,9 @@ __global__ __launch_bounds__(kSWv * kWave, 1) void sankoff_site_kernel(SiteArgs 
     const bool want_marg = A.marg != nullptr;
     const rsrc_t rmg = make_rsrc(want_marg ? A.marg + (size_t)tree * ni * L * Q : A.dp, treebytes);
     int8_t* at = A.anc ? A.anc + (size_t)tree * ni * L + site : nullptr;
-#ifndef SITE_EMIT_T
-#define SITE_EMIT_T 0  // 1: marginal rows through the transposed store (slower, PERFLOG)
-#endif
+    // marginal rows by the direct store (the transposed one was slower, PERFLOG)
     auto emit = [&](int row, const float (&g)[kSQ]) {
-      if (want_marg) {
-        if (SITE_EMIT_T)
-          store_row(rmg, row, g);
-        else
-          store_row_direct(rmg, row, g);
-      }
+      if (want_marg) store_row_direct(rmg, row, g);
       if (at && active) {
         float bv = g[0];
         int bi = 0;
@@ -914,9 +746,9 @@ __global__ __launch_bounds__(kSWv * kWave, 1) void sankoff_site_kernel(SiteArgs 
             if (ie.w > 1 && keep_s) {
               // the forward's D and s rows of this child (no mat-vec)
               float sv[kSQ], md, u[kSQ];
-              load_row(SITE_ADJ_ROW(ie.x), d);
+              load_row(ie.x, d);
               weights_u(d, md, u);
-              load_row_r(rsr, SITE_ADJ_ROW(ie.x), sv);
+              load_row_r(rsr, ie.x, sv);
               // lanes past L read 0 (their g is 0): keep r = g / s finite
 #pragma unroll
               for (int i = 0; i < kSQ; ++i) sv[i] = active ? sv[i] : 1.0f;
@@ -991,6 +823,19 @@ __global__ __launch_bounds__(kSWv * kWave, 1) void sankoff_site_kernel(SiteArgs 
   }
 }
 
+// One launch of an instantiation.  Its dynamic-LDS ceiling is set once, the
+// first time it is launched, to the CU's whole LDS: a later call's tree may
+// need more than this call's.
+template <int PHASE, int QC, bool KS = false, bool CH = true>
+void launch_site(const SiteArgs& A, size_t lds, hipStream_t st) {
+  static const hipError_t attr =
+      hipFuncSetAttribute(reinterpret_cast<const void*>(sankoff_site_kernel<PHASE, QC, KS, CH>),
+                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsPerCu);
+  (void)attr;
+  hipLaunchKernelGGL((sankoff_site_kernel<PHASE, QC, KS, CH>), dim3(A.B * A.tiles), dim3(kSWv * kWave), lds,
+                     st, A);
+}
+
 }  // namespace
 
 #ifdef TREX_SITE_TIMING
@@ -1019,7 +864,7 @@ bool site_eligible(const WideCall& c, int lp_slots) {
   const char* e = std::getenv("TREX_SITE");  // "0": the state-parallel kernel (A/B)
   if (e && e[0] == '0') return false;
   if ((int64_t)c.ni * c.L * c.Q * 4 > 0x7FFFFFF0LL) return false;
-  return site_lds_bytes(lp_slots, c.nl, c.ni) <= 160 * 1024;
+  return site_lds_bytes(lp_slots, c.nl, c.ni) <= kLdsPerCu;
 }
 
 int site_run(const char* fn, const WideCall& c, const int32_t* lanes, int lp_slots,
@@ -1028,72 +873,39 @@ int site_run(const char* fn, const WideCall& c, const int32_t* lanes, int lp_slo
   const size_t lds = site_lds_bytes(lp_slots, c.nl, c.ni);
   if ((int64_t)c.B * tiles > 0x7FFFFFFF) return set_error(TREX_E_ARG, "%s: grid too large", fn);
   hipStream_t st = (hipStream_t)c.stream;
-  SiteArgs A;
-  A.lanes = lanes;
-  A.stride = lp_tree_ints(c.ni);
-  A.leaves = c.leaves;
-  A.cost = c.cost;
-  A.n_int = c.ni;
-  A.nl = c.nl;
-  A.L = c.L;
-  A.tiles = tiles;
-  A.B = c.B;
-  A.Q = c.Q;
-  A.a = c.a;
-  A.bcoef = c.bcoef;
-  A.hard_root = c.hard_root;
-  A.dp = c.dp;
-  A.site_score = c.site_score;
-  A.dts = c.dts;
-  A.marg = c.marg;
-  A.anc = c.anc;
-  const int64_t nb = (int64_t)c.B * tiles;
-  A.part_tree = static_cast<double*>(c.workspace);
-  A.part_dc = A.part_tree + nb;
-  A.kg = kg;
-  A.ptab = kg - kSiteTabBytes / 4;
-  A.srow = c.phase == 3 ? c.site_srow : nullptr;
+  SiteArgs A = site_args<SiteArgs>(c, lanes, lp_slots, flag, kg, tiles);
   {
     const char* e = std::getenv("TREX_SITE_CHERRY");  // read per call (tests flip it)
     A.cherry = !(e && e[0] == '0');
   }
-  A.flag = flag;
-  A.n_slots = lp_slots;
-  auto go = [&](auto kernel) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(kernel, dim3((int)nb), dim3(kSWv * kWave), lds, st, A);
-  };
   const bool ks = A.srow != nullptr;
   if (c.Q == kSQ && !A.cherry) {  // A/B: no cherry tables, no kept s rows
     if (c.phase == 1)
-      go(sankoff_site_kernel<1, kSQ, false, false>);
+      launch_site<1, kSQ, false, false>(A, lds, st);
     else if (c.phase == 2)
-      go(sankoff_site_kernel<2, kSQ, false, false>);
+      launch_site<2, kSQ, false, false>(A, lds, st);
     else
-      go(sankoff_site_kernel<3, kSQ, false, false>);
+      launch_site<3, kSQ, false, false>(A, lds, st);
   } else if (c.Q == kSQ) {
     if (c.phase == 1)
-      go(sankoff_site_kernel<1, kSQ>);
+      launch_site<1, kSQ>(A, lds, st);
     else if (c.phase == 2)
-      go(sankoff_site_kernel<2, kSQ>);
+      launch_site<2, kSQ>(A, lds, st);
     else if (ks)
-      go(sankoff_site_kernel<3, kSQ, true>);
+      launch_site<3, kSQ, true>(A, lds, st);
     else
-      go(sankoff_site_kernel<3, kSQ>);
+      launch_site<3, kSQ>(A, lds, st);
   } else {
     if (c.phase == 1)
-      go(sankoff_site_kernel<1, 0>);
+      launch_site<1, 0>(A, lds, st);
     else if (c.phase == 2)
-      go(sankoff_site_kernel<2, 0>);
+      launch_site<2, 0>(A, lds, st);
     else if (ks)
-      go(sankoff_site_kernel<3, 0, true>);
+      launch_site<3, 0, true>(A, lds, st);
     else
-      go(sankoff_site_kernel<3, 0>);
+      launch_site<3, 0>(A, lds, st);
   }
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return set_error(TREX_E_HIP, "%s: %s", fn, hipGetErrorString(e));
-  return TREX_OK;
+  return hip_check(fn);
 }
 
 }  // namespace trex

@@ -24,48 +24,22 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cmath>
-#include <cstdlib>
 #include <type_traits>
 
-#include "sankoff_dev.h"
-#include "trex_common.h"
-#include "wide_dev.h"
+#include "site_dev.h"
 
 namespace trex {
 
 namespace {
 
-constexpr int kSQ2 = kSiteSQ;                 // states of a site (Q padded to 20)
-constexpr int kH = kSQ2 / 2;                  // states per wave
-constexpr int kSlotF2 = kSQ2 * kWave;         // floats per slot / scratch vector
-constexpr int kTabF2 = (kSQ2 + 1) * kSQ2 + kSQ2;  // T[Q + 1][kSQ] + 1 / sum_j K_ij
-constexpr int kScrF = kSQ2 * (kWave + 4) - 4;  // floats per pair scratch vector (padded rows; the last row's pad dropped)
+constexpr int kH = kSQ / 2;                   // states per wave
+constexpr int kScrF = kSQ * (kWave + 4) - 4;  // floats per pair scratch vector (padded rows; the last row's pad dropped)
 
 typedef float f4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8v __attribute__((ext_vector_type(8)));
 
-// eight floats (two float4 at p0, p1) split exactly into truncated bf16
-// pieces x = h + m + l, packed two per dword in k order (sankoff_site.hip)
-__device__ __forceinline__ void split3p(const float* p0, const float* p1, u32x4& h, u32x4& m,
-                                        u32x4& l) {
-  const float4 a = *reinterpret_cast<const float4*>(p0), b = *reinterpret_cast<const float4*>(p1);
-  const float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    typedef unsigned int u2 __attribute__((ext_vector_type(2)));
-    const f2 x = pk(v[2 * q], v[2 * q + 1]);
-    const u2 xb = __builtin_bit_cast(u2, x);
-    const f2 r1 = x - __builtin_bit_cast(f2, xb & 0xFFFF0000u);
-    const u2 mb = __builtin_bit_cast(u2, r1) & 0xFFFF0000u;
-    const u2 lb = __builtin_bit_cast(u2, r1 - __builtin_bit_cast(f2, mb));
-    h[q] = __builtin_amdgcn_perm(xb.y, xb.x, 0x07060302u);
-    m[q] = __builtin_amdgcn_perm(mb.y, mb.x, 0x07060302u);
-    l[q] = __builtin_amdgcn_perm(lb.y, lb.x, 0x07060302u);
-  }
-}
-
-
+// SiteArgs without cherry, and a struct of its own for it: behind the extra
+// word srow, flag and n_slots move in the kernarg segment, and the six
+// KS = true kernels' register allocation with them (PERFLOG)
 struct Site2Args {
   const int* lanes;
   int64_t stride;
@@ -89,24 +63,15 @@ struct Site2Args {
 };
 
 #ifdef TREX_SITE2_TIMING
-// diagnostic build (tools/build_ab.sh s2t sankoff_site2.hip -DTREX_SITE2_TIMING):
-// lane 0 of every wave of the first 2048 workgroups stamps s_memtime at the
-// phase boundaries of sankoff_site.hip's SITE_STAMP (tools/site_times.py --pair)
+// tools/build_ab.sh s2t sankoff_site2.hip -DTREX_SITE2_TIMING: the phase
+// boundaries of sankoff_site.hip's stamps (tools/site_times.py --pair)
 __device__ unsigned long long g_site2_t[2048][16][20];
-#define SITE2_STAMP(j)                                                             \
-  do {                                                                             \
-    if ((threadIdx.x & 63) == 0 && blockIdx.x < 2048 && (j) < 20)                  \
-      g_site2_t[blockIdx.x][threadIdx.x >> 6][j] = __builtin_amdgcn_s_memtime();  \
-  } while (0)
+#define SITE2_STAMP(j) SITE_STAMP_TO(g_site2_t, j)
 #else
 #define SITE2_STAMP(j) \
   do {                 \
   } while (0)
 #endif
-
-__device__ __forceinline__ void site2_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
 
 // transposed scratch rows padded to 68 floats: row i, site s at i * 68 + s.
 // 16 rows read at one site group start in 16 distinct 16-byte bank groups
@@ -145,14 +110,14 @@ __global__ __launch_bounds__(2 * NP * kWave, 1) void sankoff_site2_kernel(Site2A
   // ---- LDS: slots [n_slots][kSQ][64] | pair scratch [8][2][kSQ][64] |
   // exchange [2][8][2][64] | flags [16] (+pad) | T, sinv | program | leaf codes ----
   float* slots = lds;
-  float* scr = slots + (size_t)A.n_slots * kSlotF2;
+  float* scr = slots + (size_t)A.n_slots * kSlotF;
   float* xr = scr + (size_t)pr * 2 * kScrF;
   float* xu = xr + kScrF;
   float* ex = scr + (size_t)kPairs * 2 * kScrF;
   volatile int* flags = reinterpret_cast<volatile int*>(ex + kExF);  // [16]
   float* tab = ex + kExF + 16;
-  float* sinv = tab + (kSQ2 + 1) * kSQ2;
-  int* lprog = reinterpret_cast<int*>(tab + kTabF2);
+  float* sinv = tab + (kSQ + 1) * kSQ;
+  int* lprog = reinterpret_cast<int*>(tab + kTabF);
   const int pints = (int)A.stride;
   int8_t* lleaf = reinterpret_cast<int8_t*>(lprog + pints);
 
@@ -164,15 +129,11 @@ __global__ __launch_bounds__(2 * NP * kWave, 1) void sankoff_site2_kernel(Site2A
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     ++sync_n;
     flags[wv] = sync_n;
-#ifndef SITE2_DIAG_NOSYNC  // diagnostic: no waiting for the partner (wrong results; the syncs' cost)
     int guard = 0;
     while (__builtin_amdgcn_readfirstlane(flags[wv ^ 1]) < sync_n) {
-#ifndef SITE2_NOSLEEP
       __builtin_amdgcn_s_sleep(1);
-#endif
       if (++guard > (1 << 22)) break;  // never expected: the results are then wrong (tests)
     }
-#endif
     asm volatile("" ::: "memory");
   };
   // one value per lane to the partner (two alternating buffers: a buffer is
@@ -188,32 +149,22 @@ __global__ __launch_bounds__(2 * NP * kWave, 1) void sankoff_site2_kernel(Site2A
     return o;
   };
 
-  float cmin;
-  {
-    float lmin = INFINITY;
-    for (int e = lane; e < Q * Q; e += kWave) lmin = fminf(lmin, A.cost[e]);
-    cmin = uniform(wave_minf(lmin));
-  }
-  for (int e = threadIdx.x; e < (kSQ2 + 1) * kSQ2; e += kSW2 * kWave) {
-    const int code = e / kSQ2, i = e - code * kSQ2;
+  const float cmin = site_cost_min(A.cost, Q, lane);
+  for (int e = threadIdx.x; e < (kSQ + 1) * kSQ; e += kSW2 * kWave) {
+    const int code = e / kSQ, i = e - code * kSQ;
     float v = 0.0f;
     if (i < Q) {
       if (code < Q) {
         v = A.cost[i * Q + code];
       } else {
         float sk = 0.0f;
-        for (int j = 0; j < Q; ++j) sk += A.kg[i * kSQ2 + j];
+        for (int j = 0; j < Q; ++j) sk += A.kg[i * kSQ + j];
         v = fmaf(-bcoef, fast_log2(sk), kSentinel + cmin);
       }
     }
     tab[e] = v;
   }
-  if (threadIdx.x < kSQ2) {
-    const int i = threadIdx.x;
-    float sk = 0.0f;
-    for (int j = 0; j < Q; ++j) sk += A.kg[i * kSQ2 + j];
-    sinv[i] = i < Q ? __builtin_amdgcn_rcpf(sk) : 0.0f;
-  }
+  site_row_sum_inv(A.kg, Q, sinv);
   if (threadIdx.x < kSW2) flags[threadIdx.x] = 0;
   {
     const int* pg = A.lanes + (size_t)tree * A.stride;
@@ -266,7 +217,7 @@ __global__ __launch_bounds__(2 * NP * kWave, 1) void sankoff_site2_kernel(Site2A
   // instruction 1 KiB contiguous (sankoff_site.hip store_row)
   auto store_row = [&](rsrc_t r, int row, const float (&v)[kH]) {
     pair_sync();  // the partner is done reading xr
-    if (QC == kSQ2) {
+    if (QC == kSQ) {
       // 8-byte aligned pairs (Q and s0 even)
 #pragma unroll
       for (int k = 0; k < kH; k += 2)
@@ -317,7 +268,7 @@ __global__ __launch_bounds__(2 * NP * kWave, 1) void sankoff_site2_kernel(Site2A
   };
   typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
   auto store_row_direct = [&](rsrc_t r, int row, const float (&v)[kH]) {
-    if constexpr (QC == kSQ2) {
+    if constexpr (QC == kSQ) {
       const uint32_t so = row * rowbytes;
       if (hf == 0) {
         const u32x4 w0 = u4(v[0], v[1], v[2], v[3]), w1 = u4(v[4], v[5], v[6], v[7]);
@@ -346,7 +297,7 @@ __global__ __launch_bounds__(2 * NP * kWave, 1) void sankoff_site2_kernel(Site2A
     }
   };
   auto load_row_r = [&](rsrc_t rr, int row, float (&v)[kH]) {
-    if constexpr (QC == kSQ2) {
+    if constexpr (QC == kSQ) {
       const uint32_t so = row * rowbytes;
       u32x4 a, b;
       u32x2 c;
@@ -376,16 +327,16 @@ __global__ __launch_bounds__(2 * NP * kWave, 1) void sankoff_site2_kernel(Site2A
   auto load_row = [&](int row, float (&v)[kH]) { load_row_r(rdp, row, v); };
   auto slot_get = [&](int sl, float (&v)[kH]) {
 #pragma unroll
-    for (int k = 0; k < kH; ++k) v[k] = slots[(size_t)sl * kSlotF2 + (s0 + k) * kWave + lane];
+    for (int k = 0; k < kH; ++k) v[k] = slots[(size_t)sl * kSlotF + (s0 + k) * kWave + lane];
   };
   auto slot_put = [&](int sl, const float (&v)[kH]) {
 #pragma unroll
-    for (int k = 0; k < kH; ++k) slots[(size_t)sl * kSlotF2 + (s0 + k) * kWave + lane] = v[k];
+    for (int k = 0; k < kH; ++k) slots[(size_t)sl * kSlotF + (s0 + k) * kWave + lane] = v[k];
   };
   auto tab_row = [&](int code, float (&m)[kH]) {
 #pragma unroll
     for (int c = 0; c < kH / 2; ++c) {
-      const float2 w = reinterpret_cast<const float2*>(tab + code * kSQ2 + s0)[c];
+      const float2 w = reinterpret_cast<const float2*>(tab + code * kSQ + s0)[c];
       m[2 * c] = w.x;
       m[2 * c + 1] = w.y;
     }
@@ -394,10 +345,10 @@ __global__ __launch_bounds__(2 * NP * kWave, 1) void sankoff_site2_kernel(Site2A
     return ((desc >> 24) & 3) == kKindLeaf ? (int)lleaf[(desc & 0xFFFF) * kWave + lane] : Q;
   };
   const float* tmg = A.ptab;
-  const float* tsg = A.ptab + kSitePairs * kSQ2;
+  const float* tsg = A.ptab + kSitePairs * kSQ;
   auto pair_of = [&](const I4& e) -> int { return site_pair(leaf_code(e.y), leaf_code(e.z)); };
   auto load_tab = [&](const float* t, int p, float (&v)[kH]) {
-    const float2* r = reinterpret_cast<const float2*>(t + p * kSQ2 + s0);
+    const float2* r = reinterpret_cast<const float2*>(t + p * kSQ + s0);
 #pragma unroll
     for (int c = 0; c < kH / 2; ++c) {
       const float2 w = r[c];
@@ -428,10 +379,10 @@ __global__ __launch_bounds__(2 * NP * kWave, 1) void sankoff_site2_kernel(Site2A
     f2 s2[kH / 2];
 #pragma unroll
     for (int k = 0; k < kH / 2; ++k) s2[k] = pk(0.0f, 0.0f);
-    const cptr<float> KT = K + kSQ2 * kSQ2 + s0;
+    const cptr<float> KT = K + kSQ * kSQ + s0;
 #pragma unroll 2
     for (int j = 0; j < Q; ++j) {
-      const cptr<float> kc = KT + j * kSQ2;
+      const cptr<float> kc = KT + j * kSQ;
       const float uj = xu[j * kWave + lane];
 #pragma unroll
       for (int k = 0; k < kH; k += 2) s2[k / 2] = __builtin_elementwise_fma(pk(kc[k], kc[k + 1]), pk(uj, uj), s2[k / 2]);
@@ -535,7 +486,7 @@ __global__ __launch_bounds__(2 * NP * kWave, 1) void sankoff_site2_kernel(Site2A
         }
       }
       if (split) {
-        site2_barrier();
+        site_barrier();
         if (pr < nit && (pr & 1) == 0) {
           const float* px = scr + (size_t)(pr + 1) * 2 * kScrF + kScrF;  // pair pr + 1's xu
 #pragma unroll
@@ -544,7 +495,7 @@ __global__ __launch_bounds__(2 * NP * kWave, 1) void sankoff_site2_kernel(Site2A
           slot_put((stp.x >> 16) & 0xFF, dv);
         }
       }
-      site2_barrier();
+      site_barrier();
       SITE2_STAMP(2 + (s < 5 ? s : 5));
     }
   }
@@ -554,34 +505,34 @@ __global__ __launch_bounds__(2 * NP * kWave, 1) void sankoff_site2_kernel(Site2A
   // sankoff_site.hip, so score and cotangent are bitwise that kernel's ----
   const int root_slot = (load_step(steps, pword(4 + S - 1)).x >> 16) & 0xFF;
   if (wv == 0) {
-    float droot[kSQ2], groot[kSQ2];
+    float droot[kSQ], groot[kSQ];
     if constexpr (FWD) {
 #pragma unroll
-      for (int i = 0; i < kSQ2; ++i) droot[i] = slots[(size_t)root_slot * kSlotF2 + i * kWave + lane];
+      for (int i = 0; i < kSQ; ++i) droot[i] = slots[(size_t)root_slot * kSlotF + i * kWave + lane];
     } else {
       const int vb = active ? site * Q * 4 : 0x7FFFFFF0;
 #pragma unroll
-      for (int i = 0; i < kSQ2; ++i)
+      for (int i = 0; i < kSQ; ++i)
         droot[i] = i < Q ? __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rdp, vb + 4 * i,
                                                                                 (ni - 1) * rowbytes, 1))
                          : 0.0f;
     }
     float mn = droot[0];
 #pragma unroll
-    for (int i = 1; i < kSQ2; ++i) mn = i < Q ? fminf(mn, droot[i]) : mn;
+    for (int i = 1; i < kSQ; ++i) mn = i < Q ? fminf(mn, droot[i]) : mn;
     float score;
     if (A.hard_root) {
       float cnt = 0.0f;
 #pragma unroll
-      for (int i = 0; i < kSQ2; ++i) cnt += (i < Q && droot[i] == mn) ? 1.0f : 0.0f;
+      for (int i = 0; i < kSQ; ++i) cnt += (i < Q && droot[i] == mn) ? 1.0f : 0.0f;
       const float r = 1.0f / cnt;
 #pragma unroll
-      for (int i = 0; i < kSQ2; ++i) groot[i] = (i < Q && droot[i] == mn) ? r : 0.0f;
+      for (int i = 0; i < kSQ; ++i) groot[i] = (i < Q && droot[i] == mn) ? r : 0.0f;
       score = mn;
     } else {
       float ls = 0.0f, lt = 0.0f;
 #pragma unroll
-      for (int i = 0; i < kSQ2; ++i) {
+      for (int i = 0; i < kSQ; ++i) {
         groot[i] = i < Q ? fast_exp2((mn - droot[i]) * a) : 0.0f;
         const bool tie = i < Q && droot[i] == mn;
         ls += tie ? 0.0f : groot[i];
@@ -590,7 +541,7 @@ __global__ __launch_bounds__(2 * NP * kWave, 1) void sankoff_site2_kernel(Site2A
       const float sum = lt + ls;
       const float rs = __builtin_amdgcn_rcpf(sum);
 #pragma unroll
-      for (int i = 0; i < kSQ2; ++i) groot[i] *= rs;
+      for (int i = 0; i < kSQ; ++i) groot[i] *= rs;
       score = fmaf(-bcoef, fast_log2(sum), mn);
     }
     if constexpr (FWD) {
@@ -600,10 +551,10 @@ __global__ __launch_bounds__(2 * NP * kWave, 1) void sankoff_site2_kernel(Site2A
     }
     const float f = active ? (A.dts ? as_const(A.dts)[tree] : 1.0f) : 0.0f;
 #pragma unroll
-    for (int i = 0; i < kSQ2; ++i) groot[i] *= f;
+    for (int i = 0; i < kSQ; ++i) groot[i] *= f;
     if constexpr (BWD) {
 #pragma unroll
-      for (int i = 0; i < kSQ2; ++i) slots[(size_t)root_slot * kSlotF2 + i * kWave + lane] = groot[i];
+      for (int i = 0; i < kSQ; ++i) slots[(size_t)root_slot * kSlotF + i * kWave + lane] = groot[i];
     }
   }
 
@@ -626,10 +577,10 @@ __global__ __launch_bounds__(2 * NP * kWave, 1) void sankoff_site2_kernel(Site2A
         acc2[c][r] = 0.0f;
       }
     const int l16 = lane & 15, kq = lane >> 4;  // operand row / column; k group (8 sites)
-    const int arow = 16 * hf + l16 < kSQ2 ? 16 * hf + l16 : 0;  // rows >= 20: any finite data
-    const int bcol0 = l16, bcol1 = 16 + l16 < kSQ2 ? 16 + l16 : 0;
+    const int arow = 16 * hf + l16 < kSQ ? 16 * hf + l16 : 0;  // rows >= 20: any finite data
+    const int bcol0 = l16, bcol1 = 16 + l16 < kSQ ? 16 + l16 : 0;
     auto mf = [&](const u32x4& x, const u32x4& y, f4& c) {
-      c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8v, x), __builtin_bit_cast(bf16x8v, y),
+      c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, x), __builtin_bit_cast(bf16x8, y),
                                                   c, 0, 0, 0);
     };
     // acc1 += (xr)(xu)^T: r and u split exactly into three truncated bf16
@@ -640,12 +591,12 @@ __global__ __launch_bounds__(2 * NP * kWave, 1) void sankoff_site2_kernel(Site2A
         asm volatile("" ::: "memory");  // one k-step's pieces live at a time
         const int sg = 32 * ks + 8 * kq;
         u32x4 ah, am, al;
-        split3p(xr + swz2(arow, sg), xr + swz2(arow, sg + 4), ah, am, al);
+        split3(xr + swz2(arow, sg), xr + swz2(arow, sg + 4), ah, am, al);
 #pragma unroll
         for (int c = 0; c < 2; ++c) {
           const int bc = c == 0 ? bcol0 : bcol1;
           u32x4 bh, bm, bl;
-          split3p(xu + swz2(bc, sg), xu + swz2(bc, sg + 4), bh, bm, bl);
+          split3(xu + swz2(bc, sg), xu + swz2(bc, sg + 4), bh, bm, bl);
           mf(ah, bl, acc1[c]);
           mf(al, bh, acc1[c]);
           mf(am, bm, acc1[c]);
@@ -680,7 +631,7 @@ __global__ __launch_bounds__(2 * NP * kWave, 1) void sankoff_site2_kernel(Site2A
         asm volatile("" ::: "memory");
         const int sg = 32 * ks + 8 * kq;
         u32x4 ph, pm, pl;
-        split3p(xr + swz2(arow, sg), xr + swz2(arow, sg + 4), ph, pm, pl);
+        split3(xr + swz2(arow, sg), xr + swz2(arow, sg + 4), ph, pm, pl);
         const uint32_t w0[2] = {l0 ? c0[sg >> 2] : 0xFFFFFFFFu, l0 ? c0[(sg >> 2) + 1] : 0xFFFFFFFFu};
         const uint32_t w1[2] = {l1 ? c1[sg >> 2] : 0xFFFFFFFFu, l1 ? c1[(sg >> 2) + 1] : 0xFFFFFFFFu};
 #pragma unroll
@@ -725,7 +676,7 @@ __global__ __launch_bounds__(2 * NP * kWave, 1) void sankoff_site2_kernel(Site2A
       for (int k = 0; k < kH / 2; ++k) t2[k] = pk(0.0f, 0.0f);
 #pragma unroll 2
       for (int i = 0; i < Q; ++i) {
-        const cptr<float> kr = K + i * kSQ2 + s0;
+        const cptr<float> kr = K + i * kSQ + s0;
         const float ri = xr[swz2(i, lane)];
 #pragma unroll
         for (int k = 0; k < kH; k += 2)
@@ -880,7 +831,7 @@ __global__ __launch_bounds__(2 * NP * kWave, 1) void sankoff_site2_kernel(Site2A
         const int c_lo = split ? (it & 1) : 0;
         adj_task(load_step(steps, lo + (split ? it >> 1 : it)), c_lo, split ? c_lo + 1 : 2);
       }
-      site2_barrier();
+      site_barrier();
       SITE2_STAMP(10 + (S - 1 - s < 5 ? S - 1 - s : 5));
     }
 
@@ -896,7 +847,7 @@ __global__ __launch_bounds__(2 * NP * kWave, 1) void sankoff_site2_kernel(Site2A
       for (int r = 0; r < 4; ++r) {
         const int i = 16 * hf + 4 * kq + r, j = 16 * c + l16;
         if (i < Q && j < Q)
-          red[(size_t)pr * Q2 + i * Q + j] = (double)acc1[c][r] * (double)K[i * kSQ2 + j] + (double)acc2[c][r];
+          red[(size_t)pr * Q2 + i * Q + j] = (double)acc1[c][r] * (double)K[i * kSQ + j] + (double)acc2[c][r];
       }
     __syncthreads();
     const int nb = A.B * A.tiles;
@@ -910,10 +861,22 @@ __global__ __launch_bounds__(2 * NP * kWave, 1) void sankoff_site2_kernel(Site2A
   }
 }
 
+// One launch of an instantiation; its dynamic-LDS ceiling set once, to the
+// CU's whole LDS (sankoff_site.hip launch_site)
+template <int PHASE, int QC, bool KS, int NP>
+void launch_site2(const Site2Args& A, size_t lds, hipStream_t st) {
+  static const hipError_t attr =
+      hipFuncSetAttribute(reinterpret_cast<const void*>(sankoff_site2_kernel<PHASE, QC, KS, NP>),
+                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsPerCu);
+  (void)attr;
+  hipLaunchKernelGGL((sankoff_site2_kernel<PHASE, QC, KS, NP>), dim3(A.B * A.tiles), dim3(2 * NP * kWave), lds,
+                     st, A);
+}
+
 }  // namespace
 
 size_t site2_lds_bytes(int np, int n_slots, int nl, int ni) {
-  const size_t b = ((size_t)n_slots * kSlotF2 + (size_t)np * 2 * kScrF + 2 * np * 2 * kWave + 16 + kTabF2 +
+  const size_t b = ((size_t)n_slots * kSlotF + (size_t)np * 2 * kScrF + 2 * np * 2 * kWave + 16 + kTabF +
                     lp_tree_ints(ni)) * 4 +
                    (size_t)nl * kWave;
   return (b + 15) & ~(size_t)15;
@@ -927,7 +890,7 @@ static int site2_pairs(int lp_slots, int nl, int ni) {
   if (!e || e[0] < '1' || e[0] > '9') return 0;
   const int want = e[0] == '1' ? 0 : e[0] - '0';
   for (int np : {8, 6, 4})
-    if ((want == 0 || want == np) && site2_lds_bytes(np, lp_slots, nl, ni) <= 160 * 1024) return np;
+    if ((want == 0 || want == np) && site2_lds_bytes(np, lp_slots, nl, ni) <= kLdsPerCu) return np;
   return 0;
 }
 
@@ -943,59 +906,28 @@ int site2_run(const char* fn, const WideCall& c, const int32_t* lanes, int lp_sl
   const size_t lds = site2_lds_bytes(np, lp_slots, c.nl, c.ni);
   if ((int64_t)c.B * tiles > 0x7FFFFFFF) return set_error(TREX_E_ARG, "%s: grid too large", fn);
   hipStream_t st = (hipStream_t)c.stream;
-  Site2Args A;
-  A.lanes = lanes;
-  A.stride = lp_tree_ints(c.ni);
-  A.leaves = c.leaves;
-  A.cost = c.cost;
-  A.n_int = c.ni;
-  A.nl = c.nl;
-  A.L = c.L;
-  A.tiles = tiles;
-  A.B = c.B;
-  A.Q = c.Q;
-  A.a = c.a;
-  A.bcoef = c.bcoef;
-  A.hard_root = c.hard_root;
-  A.dp = c.dp;
-  A.site_score = c.site_score;
-  A.dts = c.dts;
-  A.marg = c.marg;
-  A.anc = c.anc;
-  const int64_t nb = (int64_t)c.B * tiles;
-  A.part_tree = static_cast<double*>(c.workspace);
-  A.part_dc = A.part_tree + nb;
-  A.kg = kg;
-  A.ptab = kg - kSiteTabBytes / 4;
-  A.srow = c.phase == 3 ? c.site_srow : nullptr;
-  A.flag = flag;
-  A.n_slots = lp_slots;
-  auto go = [&](auto kernel, int npairs) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(kernel, dim3((int)nb), dim3(2 * npairs * kWave), lds, st, A);
-  };
+  const Site2Args A = site_args<Site2Args>(c, lanes, lp_slots, flag, kg, tiles);
   auto pick = [&](auto np_c) {
     constexpr int NP = decltype(np_c)::value;
     const bool ks = A.srow != nullptr;
-    if (c.Q == kSQ2) {
+    if (c.Q == kSQ) {
       if (c.phase == 1)
-        go(sankoff_site2_kernel<1, kSQ2, false, NP>, NP);
+        launch_site2<1, kSQ, false, NP>(A, lds, st);
       else if (c.phase == 2)
-        go(sankoff_site2_kernel<2, kSQ2, false, NP>, NP);
+        launch_site2<2, kSQ, false, NP>(A, lds, st);
       else if (ks)
-        go(sankoff_site2_kernel<3, kSQ2, true, NP>, NP);
+        launch_site2<3, kSQ, true, NP>(A, lds, st);
       else
-        go(sankoff_site2_kernel<3, kSQ2, false, NP>, NP);
+        launch_site2<3, kSQ, false, NP>(A, lds, st);
     } else {
       if (c.phase == 1)
-        go(sankoff_site2_kernel<1, 0, false, NP>, NP);
+        launch_site2<1, 0, false, NP>(A, lds, st);
       else if (c.phase == 2)
-        go(sankoff_site2_kernel<2, 0, false, NP>, NP);
+        launch_site2<2, 0, false, NP>(A, lds, st);
       else if (ks)
-        go(sankoff_site2_kernel<3, 0, true, NP>, NP);
+        launch_site2<3, 0, true, NP>(A, lds, st);
       else
-        go(sankoff_site2_kernel<3, 0, false, NP>, NP);
+        launch_site2<3, 0, false, NP>(A, lds, st);
     }
   };
   if (np == 8)
@@ -1004,8 +936,7 @@ int site2_run(const char* fn, const WideCall& c, const int32_t* lanes, int lp_sl
     pick(std::integral_constant<int, 6>());
   else
     pick(std::integral_constant<int, 4>());
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return set_error(TREX_E_HIP, "%s: %s", fn, hipGetErrorString(e));
+  if (int e = hip_check(fn)) return e;
   ++g_site2_launches;
   return TREX_OK;
 }

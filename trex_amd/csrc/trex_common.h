@@ -12,6 +12,7 @@
 namespace trex {
 
 constexpr int32_t kPlanMagic = 0x54524558;  // 'TREX'
+constexpr size_t kLdsPerCu = 160 * 1024;    // gfx950: LDS bytes of a CU, the most one workgroup can take
 
 // forward-step child descriptor: index bits 0-15, slot 16-23, kind 24-25
 constexpr int32_t kStepAccumulate = 1 << 26;  // adjoint: add into the slot
