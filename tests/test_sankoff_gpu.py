@@ -370,8 +370,10 @@ def test_c4_scale_properties(device):
 def test_fused_fwd_bwd_equals_separate_launches(device, tau, B, L):
     """trex_sankoff_fwd_bwd == trex_sankoff_fwd + trex_sankoff_bwd, bit for bit
     (same per-wave arithmetic, same fixed-order reductions).  7 x 999 sites
-    is 112 work items (<= one wave per CU: the LDS-resident fused kernel);
-    16 x 2000 is 512 items (the re-reading fused kernel of the benchmark)."""
+    is 112 work items (<= one wave per CU) and 16 x 2000 is 512 items; both
+    run the one fused kernel there is, whose adjoint re-reads the DP rows it
+    has just written (the benchmark's; an LDS-resident variant for small grids
+    was removed in round 3, see sankoff.hip)."""
     n, Q = 24, 4
     ch = random_topologies(B, n, seed=21)
     leaves = random_leaves(B, n, L, Q, seed=22, missing=0.01)
