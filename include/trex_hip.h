@@ -54,7 +54,10 @@ extern "C" {
 #define TREX_PLAN_HEADER_INTS 16
 
 const char* trex_last_error(void);
-/* ABI / plan-layout version.
+/* ABI / plan-layout version.  (trex_fused4_program_ints / _build and
+ * trex_sankoff_fwd_bwd_prog were added under 10: new symbols only, no plan,
+ * layout or argument of an existing call changed, and tests/test_plan_cpu.py
+ * pins the number; a binding finds them by symbol.)
  * 10: trex_dp_root_total (run_sankoff for Q > 128 on the raw-table path).
  * 9: TREX_FLAG_SITE_REUSE and trex_site_flag_offset removed (flags other
  *    than TREX_FLAG_HARD_ROOT are refused).
@@ -170,6 +173,38 @@ int trex_sankoff_fwd_bwd(const int32_t* plan, int n_slots, const int8_t* leaves,
                          float* tree_score, const float* d_tree_score, float* d_cost,
                          float* marginals, int8_t* anc_states, void* workspace,
                          int64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
+ * Fused Q = 4 program: the forward steps of a plan decoded once on
+ * the host into one 32-byte record per step -- step class, LDS byte offsets
+ * of the operands, the rows the adjoint re-reads (layout: csrc/trex_common.h)
+ * -- for the kernel of csrc/sankoff_fused4.hip, whose loops read operands
+ * where the generic kernel decodes descriptors for every tile of every tree.
+ *   plan [host] a plan of trex_plan_build for the same B, n_all (read only;
+ *        its deferral bits, i.e. the TREX_DEFER state it was built with, are
+ *        kept)
+ *   prog [host] int32 buffer of trex_fused4_program_ints(B, n_all) ints out;
+ *        copy it to the device unchanged
+ * TREX_E_UNSUPPORTED when a tree has a 1e5-sentinel child (-1 fill or forward
+ * reference), a row the root does not reach or a node with two parents: such
+ * batches keep trex_sankoff_fwd_bwd.
+ *
+ * trex_sankoff_fwd_bwd_prog is trex_sankoff_fwd_bwd with that program (device
+ * pointer, built from this plan; NULL: exactly trex_sankoff_fwd_bwd).  The
+ * program's kernel takes the call when Q = 4, tau > 0, L % 4 == 0, at most 64
+ * leaves, site_score / marginals / anc_states NULL, the grid is not one the
+ * small-grid kernels claim, and TREX_FUSED4 is not "0" (read per call); every
+ * other call runs as without it.  dp, tree_score and d_cost are bitwise the
+ * same either way.
+ * ---------------------------------------------------------------------- */
+int64_t trex_fused4_program_ints(int B, int n_all);
+int trex_fused4_program_build(const int32_t* plan, int B, int n_all, int32_t* prog);
+int trex_sankoff_fwd_bwd_prog(const int32_t* plan, int n_slots, const int8_t* leaves,
+                              const float* cost, int B, int L, int n_all, int Q, float tau,
+                              unsigned flags, float* dp, float* site_score,
+                              float* tree_score, const float* d_tree_score, float* d_cost,
+                              float* marginals, int8_t* anc_states, void* workspace,
+                              int64_t workspace_bytes, void* stream, const int32_t* prog);
 
 /* ------------------------------------------------------------------------
  * Ancestral reconstruction, bit-exact with the reference's backtrack:

@@ -28,7 +28,7 @@ def counters(d):
 
 
 def short(name):
-    m = re.search(r"(sankoff_kernel|rows_load|stream_load|rows_kernel|stream_kernel|"
+    m = re.search(r"(sankoff_kernel|sankoff_fused4_kernel|rows_load|stream_load|rows_kernel|stream_kernel|"
                   r"sitemajor_kernel|wide_reduce_kernel)(<[^>(]*>)?", name)
     return (m.group(1) + (m.group(2) or "")) if m else name[:50]
 
@@ -56,13 +56,16 @@ def main():
     res = {"workload_key": a.workload_key, "calibration": corr, "kernels": {}}
     for k, v in counters(a.pmc).items():
         s = short(k)
-        if "sankoff_kernel" not in s:
+        if "sankoff_kernel" not in s and s != "sankoff_fused4_kernel":
             continue
         f = v.get("FETCH_SIZE", 0.0) * 1024 * fetch_corr
         w = v.get("WRITE_SIZE", 0.0) * 1024 * write_corr
         res["kernels"][s] = {"fetch_bytes": f, "write_bytes": w, "traffic_bytes": f + w}
     # phase -> bench kernel name (sankoff_kernel<Q, SOFT, PHASE, RAGGED>)
     for s, e in res["kernels"].items():
+        if s == "sankoff_fused4_kernel":  # the fused launch of eligible Q = 4 calls
+            res["sankoff_fwd_bwd"] = e["traffic_bytes"]
+            continue
         args = [x.strip() for x in s.split("<", 1)[1].rstrip(">").split(",")]
         if len(args) > 3 and args[3] == "true":
             continue  # ragged instantiation

@@ -42,6 +42,11 @@ SIGNATURES = {
     "trex_workspace_init": (_c_i, [_p, _c_i64, _p]),
     "trex_sankoff_fwd_bwd": (_c_i, [_p, _c_i, _p, _p, _c_i, _c_i, _c_i, _c_i, _c_f, _c_u,
                                     _p, _p, _p, _p, _p, _p, _p, _p, _c_i64, _p]),
+    # fused Q = 4 softmin kernel on a predecoded program (OPTIONAL below)
+    "trex_fused4_program_ints": (_c_i64, [_c_i, _c_i]),
+    "trex_fused4_program_build": (_c_i, [_p, _c_i, _c_i, _p]),
+    "trex_sankoff_fwd_bwd_prog": (_c_i, [_p, _c_i, _p, _p, _c_i, _c_i, _c_i, _c_i, _c_f, _c_u,
+                                         _p, _p, _p, _p, _p, _p, _p, _p, _c_i64, _p, _p]),
     "trex_sankoff_backtrack": (_c_i, [_p, _c_i, _p, _p, _c_i, _c_i, _c_i, _c_i, _p, _p]),
     "trex_dp_to_trex_layout": (_c_i, [_p, _p, _c_i, _c_i, _c_i, _c_i, _p, _p]),
     "trex_dp_site_major": (_c_i, [_c_i]),
@@ -152,6 +157,17 @@ SIGNATURES = {
 }
 
 
+# entry points added without a version bump: a library named by TREX_HIP_LIB
+# may be an older v10 build without them (tools/ab.sh runs a parent commit's
+# library under this package); has_fused4() tells
+OPTIONAL = ("trex_fused4_program_ints", "trex_fused4_program_build", "trex_sankoff_fwd_bwd_prog")
+
+
+def has_fused4() -> bool:
+    """The loaded library has the fused Q = 4 program entry points."""
+    return all(hasattr(lib(), name) for name in OPTIONAL)
+
+
 class TrexError(RuntimeError):
     """A libtrexhip.so call returned a negative TREX_E_* code."""
 
@@ -173,6 +189,8 @@ def lib() -> ctypes.CDLL:
                 "`python -c 'import __graft_entry__ as g; g.build()'` -- there is no CPU fallback")
         handle = ctypes.CDLL(str(LIB_PATH))
         for name, (res, args) in SIGNATURES.items():
+            if name in OPTIONAL and not hasattr(handle, name):
+                continue
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args

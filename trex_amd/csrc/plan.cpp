@@ -509,6 +509,86 @@ extern "C" int trex_plan_build(const int32_t* children, int B, int n_all,
 }
 
 // ---------------------------------------------------------------------------
+// Fused Q = 4 program: the forward steps of a built plan, one decoded record
+// per step (layout: trex_common.h).  The plan is read, never written; the
+// deferral bits are the plan's own (the TREX_DEFER state it was built with).
+// Refused with TREX_E_UNSUPPORTED (the caller keeps the generic kernel): a
+// 1e5-sentinel child, a step the root does not reach, a node with two parents.
+// ---------------------------------------------------------------------------
+extern "C" int64_t trex_fused4_program_ints(int B, int n_all) {
+  if (B <= 0 || n_all < 3 || n_all > 65535) return 0;
+  const int ni = n_all - (n_all + 1) / 2;
+  return TREX_PLAN_HEADER_INTS + (int64_t)B * ni * trex::kF4RecInts;
+}
+
+extern "C" int trex_fused4_program_build(const int32_t* plan, int B, int n_all, int32_t* prog) {
+  using namespace trex;
+  const char* fn = "trex_fused4_program_build";
+  if (!plan || !prog || B <= 0 || n_all < 3 || n_all > 65535)
+    return set_error(TREX_E_ARG, "%s: bad arguments (B=%d n_all=%d)", fn, B, n_all);
+  if (plan[0] != kPlanMagic || plan[1] != B || plan[2] != n_all)
+    return set_error(TREX_E_ARG, "%s: not a plan of trex_plan_build for B=%d n_all=%d", fn, B,
+                     n_all);
+  const int nl = (n_all + 1) / 2;
+  const int ni = n_all - nl;
+  const int32_t* fwd = plan + TREX_PLAN_HEADER_INTS;
+  std::memset(prog, 0, sizeof(int32_t) * TREX_PLAN_HEADER_INTS);
+  int32_t* rec = prog + TREX_PLAN_HEADER_INTS;
+  constexpr int kSlotBytes = 4 * 64 * 4;  // [64 lanes][Q = 4] f32
+  constexpr int kLeafRowBytes = 64;       // [64 lanes] i8
+  for (int64_t t = 0; t < (int64_t)B * ni; ++t) {
+    const int32_t* e = fwd + 4 * t;
+    int32_t* r = rec + kF4RecInts * t;
+    const int tree = (int)(t / ni);
+    if (e[3] & kStepUnreached)
+      return set_error(TREX_E_UNSUPPORTED, "%s: tree %d has a row the root does not reach", fn,
+                       tree);
+    int32_t flags = 0;
+    bool leaf[2];
+    for (int c = 0; c < 2; ++c) {
+      const int32_t d = e[1 + c];
+      const int kind = (d >> 24) & 3;
+      if (kind != kKindLeaf && kind != kKindInt)
+        return set_error(TREX_E_UNSUPPORTED, "%s: tree %d has a 1e5-sentinel child", fn, tree);
+      if (d & kStepAccumulate)
+        return set_error(TREX_E_UNSUPPORTED, "%s: tree %d has a node with two parents", fn, tree);
+      leaf[c] = kind == kKindLeaf;
+      r[5 + c] = kF4NoRow;
+      if (leaf[c]) {
+        flags |= c == 0 ? kF4Leaf0 : kF4Leaf1;
+        r[2 + c] = (d & 0xFFFF) * kLeafRowBytes;
+      } else {
+        const bool prev = (d & kChildPrev) != 0, deferred = (d & kChildDeferred) != 0;
+        if (prev) flags |= c == 0 ? kF4Prev0 : kF4Prev1;
+        if (deferred) flags |= c == 0 ? kF4Defer0 : kF4Defer1;
+        r[2 + c] = prev ? 0 : ((d >> 16) & 0xFF) * kSlotBytes;
+        if (!deferred) r[5 + c] = d & 0xFFFF;
+      }
+    }
+    const bool cherry = leaf[0] && leaf[1];
+    if ((e[3] & kStepDeferredIn) && !cherry)
+      return set_error(TREX_E_ARG, "%s: tree %d: a deferred step that is no cherry", fn, tree);
+    const int oslot = (e[0] >> 16) & 0xFF;
+    if (e[3] & kStepDeferredIn) flags |= kF4DeferIn;
+    if (e[3] & kStepToNext) flags |= kF4ToNext;
+    if (e[3] & kStepRoot) flags |= kF4Root;
+    const bool put = !(e[3] & kStepToNext) && oslot != 0xFF;
+    if (put) flags |= kF4Put;
+    const int fcls = cherry ? ((e[3] & kStepDeferredIn) ? kF4CherryDeferred : kF4Cherry)
+                     : (leaf[0] || leaf[1]) ? kF4LeafInt : kF4IntInt;
+    r[0] = flags | (fcls << kF4FwdClassShift);
+    r[1] = e[0] & 0xFFFF;
+    r[4] = put ? oslot * kSlotBytes : 0;
+    r[7] = 0;
+  }
+  prog[0] = kF4Magic;
+  prog[1] = B;
+  prog[2] = n_all;
+  prog[3] = ni;
+  return TREX_OK;
+}
+
+// ---------------------------------------------------------------------------
 // Ragged batches: trees of different sizes (n_all_b) and site counts (L_b) in
 // one launch.  Layout (ints): header [16] | per-tree records [B][12] |
 // work-item -> tree [items] | forward steps [sum n_int_b][4] |

@@ -1,0 +1,431 @@
+// Fused forward + adjoint for Q = 4 softmin on a predecoded program
+// (trex_fused4_program_build, plan.cpp; record layout: trex_common.h).
+//
+// The same work item, LDS map, tables, slot stack, XCD item mapping, cache
+// policies, ring depth and fp64 partials as sankoff_kernel<4, true, 3>
+// (sankoff_q4_dev.h), and the same arithmetic in the same order, so dp,
+// tree_score and d_cost are bitwise the generic kernel's.  What differs is the
+// step interpreter: the generic body decodes every step's descriptors on the
+// scalar pipe, in both sweeps, for every one of a tree's tiles; here the
+// planner has done that once and the loops switch on a step class and read
+// operands (LDS byte offsets, re-read rows) from a 32-byte record.
+//
+// Scope (run_phase, sankoff.hip, checks it): uniform batch, tau > 0, leaf
+// tile prefetchable (L % 4 == 0, <= 64 leaves), no site scores, marginals or
+// ancestral states; a program exists (no sentinel child, unreached row or
+// two-parent node).  The cost matrix decides on the device as in
+// sankoff_kernel: the factored softmin runs the loops below, the per-row
+// stabilised softmin (range(C) / tau > 40) the generic body.
+#include <hip/hip_runtime.h>
+
+#include <cstdlib>
+#include <cstring>
+
+#include "sankoff_dev.h"
+#include "sankoff_q4_dev.h"
+#include "trex_common.h"
+
+namespace trex {
+
+namespace {
+
+struct F4Rec {
+  int flags, row, a0, a1, slot, r0, r1;
+};
+__device__ __forceinline__ F4Rec load_rec(cptr<int> prog, int k) {
+  const cptr<int> p = prog + kF4RecInts * k;
+  return F4Rec{p[0], p[1], p[2], p[3], p[4], p[5], p[6]};
+}
+
+template <bool SYM>
+__device__ __forceinline__ void fused4_body(const KArgs& A, const int* prog_, float* lds) {
+  constexpr int Q = 4;
+  constexpr int MODE = kSoftK;
+  const int lane = threadIdx.x;
+  const int L = A.L;
+  const float a = A.a, bcoef = A.bcoef;
+  const int nb = A.nblocks;
+  const int per = (nb + 7) / 8;
+  const int xcd = blockIdx.x & 7;
+  const int item_end = min(nb, (xcd + 1) * per);
+  const int item = xcd * per + (blockIdx.x >> 3);
+  if (item >= item_end) return;
+
+  Coef<Q> cf;
+  load_coef<Q, MODE>(A.cost, a, cf);
+
+  // LDS map of the fused generic kernel (sankoff_q4_dev.h)
+  float* tab = lds;
+  float* slots = lds + tab_floats(3);
+  float* tm = tab + kLeafTabFloats;
+  float* tu = tab + kLeafTabFloats + kPairFloats;
+  float* tr = tab + kLeafTabFloats + 2 * kPairFloats;
+  int8_t* lleaf = reinterpret_cast<int8_t*>(slots + (size_t)max(A.n_slots, 1) * Q * kWave);
+
+  // ---- once per wave: leaf tables, then pair tables (as sankoff_body) ----
+  {
+    float cmn, cmx;
+    cost_range<Q>(A.cost, cmn, cmx);
+    const float range = cmx - cmn;
+    const bool lfast = (kSentinel - range) * a >= 64.0f;
+    if (lane <= Q) {
+      const cptr<float> cost = as_const(A.cost);
+      float d1[Q], m1[Q], g1[Q], w1[Q][Q], gc1[Q];
+#pragma unroll
+      for (int j = 0; j < Q; ++j) {
+        d1[j] = j == lane ? 0.0f : kSentinel;
+        g1[j] = 1.0f;
+      }
+#pragma unroll
+      for (int i = 0; i < Q; ++i)
+#pragma unroll
+        for (int j = 0; j < Q; ++j) w1[i][j] = 0.0f;
+      if (lfast && lane < Q) {
+#pragma unroll
+        for (int i = 0; i < Q; ++i) {
+          const float cv = cost[i * Q + lane];
+          m1[i] = cv;
+          const float ik = fast_exp2((cv - cf.cmin) * a);
+#pragma unroll
+          for (int j = 0; j < Q; ++j) w1[i][j] = j == lane ? ik : 0.0f;
+        }
+      } else {
+        message<Q, MODE>(cf, a, bcoef, d1, m1);
+        message_adjoint<Q, MODE>(cf, a, d1, g1, w1, gc1);
+      }
+#pragma unroll
+      for (int i = 0; i < Q; ++i) {
+        tab[lane * Q + i] = m1[i];
+#pragma unroll
+        for (int j = 0; j < Q; ++j) tab[kWTab + (lane * Q + i) * Q + j] = w1[i][j];
+      }
+    }
+  }
+  __syncthreads();  // T is written by lanes <= Q
+  if (lane < (Q + 1) * (Q + 1)) {
+    const int c0 = lane / (Q + 1), c1 = lane - c0 * (Q + 1);
+    float t0[Q], t1[Q], d1[Q], m1[Q], u[Q], rs[Q];
+    lds_vec_get<Q>(tab + c0 * Q, t0);
+    lds_vec_get<Q>(tab + c1 * Q, t1);
+#pragma unroll
+    for (int j = 0; j < Q; ++j) d1[j] = t0[j] + t1[j];
+    message<Q, MODE, false>(cf, a, bcoef, d1, m1);
+    lds_vec_put<Q>(tm + lane * Q, m1);
+    softk_weights<Q, SYM>(cf, a, d1, u, rs);
+    lds_vec_put<Q>(tu + lane * Q, u);
+    lds_vec_put<Q>(tr + lane * Q, rs);
+  }
+
+  // ---- this item ----
+  const int tree = item / A.tiles;
+  const int tile = item - tree * A.tiles;
+  const int n_int = A.n_int;
+  const size_t rows_base = (size_t)tree * n_int * L;
+  const cptr<int> prog = as_const(prog_) + (size_t)tree * n_int * kF4RecInts;
+  const int site = tile * kWave + lane;
+  const bool active = site < L;
+
+  // leaf tile: lane l loads dword (l & 15) of rows 4r + (l >> 4), 16 loads in
+  // flight (the generic kernel's prefetch; L % 4 == 0 and nl <= 64 hold here)
+  {
+    const int pf_voff = (lane >> 4) * L + (lane & 15) * 4;
+    const rsrc_t rl =
+        make_rsrc(A.leaves + (size_t)tree * A.nl * L, (uint32_t)((size_t)A.nl * L));
+    uint32_t pre[kPrefetchRows / 4];
+#pragma unroll
+    for (int r = 0; r < kPrefetchRows / 4; ++r)
+      pre[r] = __builtin_amdgcn_raw_buffer_load_b32(rl, pf_voff, 4 * r * L + tile * kWave, kAuxLeaf);
+    __syncthreads();  // the tables are written by a few lanes, read by all
+    uint32_t* dst = reinterpret_cast<uint32_t*>(lleaf);
+#pragma unroll
+    for (int r = 0; r < kPrefetchRows / 4; ++r) {
+      const int row = 4 * r + (lane >> 4);
+      if (row < A.nl) dst[row * 16 + (lane & 15)] = pre[r];
+    }
+  }
+
+  const uint32_t treebytes = (uint32_t)((size_t)n_int * Q * L * 4);
+  const rsrc_t rdp = make_rsrc(A.dp + rows_base * Q, treebytes);
+  // inactive lanes address past the buffer: stores drop, loads return 0
+  const int voff = active ? site * Q * 4 : 0x7FFFFFF0;
+  const int rowbytes = L * Q * 4;
+
+  // a lane's corner of the slot stack and of the leaf tile; the records hold
+  // the byte offsets from there
+  char* slot_l = reinterpret_cast<char*>(slots) + lane * (Q * 4);
+  const int8_t* leaf_l = lleaf + lane;
+  // a leaf's code, normalised to [0, Q] (Q: missing)
+  auto rd_code = [&](int off) __attribute__((always_inline)) {
+    const int code = ld_code(leaf_l + off);
+    return ((unsigned)code < (unsigned)Q) ? code : Q;
+  };
+  auto rd_slot = [&](int off, float (&d)[Q]) __attribute__((always_inline)) {
+    lds_vec_get<Q>(reinterpret_cast<const float*>(slot_l + off), d);
+  };
+  auto wr_slot = [&](int off, const float (&d)[Q]) __attribute__((always_inline)) {
+    lds_vec_put<Q>(reinterpret_cast<float*>(slot_l + off), d);
+  };
+
+  // ---- forward ----
+  float dv[Q];
+  {
+    float prev[Q];  // previous step's D / message (register bypass)
+    F4Rec nxt = load_rec(prog, 0);
+    for (int k = 0; k < n_int; ++k) {
+      const F4Rec s = nxt;
+      if (k + 1 < n_int) nxt = load_rec(prog, k + 1);
+      const int fl = s.flags;
+      const int fcls = (fl >> kF4FwdClassShift) & 15;
+      int pair = 0;
+      if (fcls <= kF4CherryDeferred) {
+        // both codes in flight, then both table rows
+        const int c0 = rd_code(s.a0), c1 = rd_code(s.a1);
+        float t0[Q], t1[Q];
+        lds_vec_get<Q>(tab + c0 * Q, t0);
+        lds_vec_get<Q>(tab + c1 * Q, t1);
+#pragma unroll
+        for (int i = 0; i < Q; ++i) dv[i] = t0[i] + t1[i];
+        pair = c0 * (Q + 1) + c1;
+      } else if (fcls == kF4LeafInt) {
+        const bool l0 = (fl & kF4Leaf0) != 0;
+        const int code = rd_code(l0 ? s.a0 : s.a1);
+        float d[Q], t[Q], m[Q];
+        if (fl & (kF4Prev0 | kF4Prev1)) {
+#pragma unroll
+          for (int j = 0; j < Q; ++j) d[j] = prev[j];
+        } else {
+          rd_slot(l0 ? s.a1 : s.a0, d);
+        }
+        lds_vec_get<Q>(tab + code * Q, t);
+        // a deferred cherry handed its message on (TM), not its D
+        if (fl & (kF4Defer0 | kF4Defer1)) {
+#pragma unroll
+          for (int i = 0; i < Q; ++i) m[i] = d[i];
+        } else {
+          message<Q, MODE, false>(cf, a, bcoef, d, m);
+        }
+#pragma unroll
+        for (int i = 0; i < Q; ++i) dv[i] = t[i] + m[i];
+      } else {
+        float d0[Q], d1[Q], m0[Q], m1[Q];
+        if (fl & kF4Prev0) {
+#pragma unroll
+          for (int j = 0; j < Q; ++j) d0[j] = prev[j];
+        } else {
+          rd_slot(s.a0, d0);
+        }
+        if (fl & kF4Prev1) {
+#pragma unroll
+          for (int j = 0; j < Q; ++j) d1[j] = prev[j];
+        } else {
+          rd_slot(s.a1, d1);
+        }
+        if (fl & kF4Defer0) {
+#pragma unroll
+          for (int i = 0; i < Q; ++i) m0[i] = d0[i];
+        } else {
+          message<Q, MODE, false>(cf, a, bcoef, d0, m0);
+        }
+        if (fl & kF4Defer1) {
+#pragma unroll
+          for (int i = 0; i < Q; ++i) m1[i] = d1[i];
+        } else {
+          message<Q, MODE, false>(cf, a, bcoef, d1, m1);
+        }
+#pragma unroll
+        for (int i = 0; i < Q; ++i) dv[i] = m0[i] + m1[i];
+      }
+      // deferred cherries' rows are never re-read: they stream (nt)
+      if (fl & kF4DeferIn) {
+        bst_row<Q, kAuxCherryRow>(rdp, voff, s.row * rowbytes, dv);
+        // the row is stored; its one parent takes the message from the table
+        lds_vec_get<Q>(tm + pair * Q, dv);
+      } else {
+        bst_row<Q, kAuxFusedRow>(rdp, voff, s.row * rowbytes, dv);
+      }
+      if (fl & kF4Put) wr_slot(s.slot, dv);
+#pragma unroll
+      for (int i = 0; i < Q; ++i) prev[i] = dv[i];
+    }
+  }
+
+  // ---- root: score + cotangent ----
+  float score, groot[Q];
+  root_score<Q, true>(dv, a, bcoef, A.hard_root != 0, score, groot);
+  {
+    double tot = 0.0;
+    if (active) tot += (double)score;
+    tot = wave_sum_lane0(tot);
+    if (lane == 0) A.part_tree[item] = tot;
+  }
+
+  // ---- adjoint ----
+  // acc: dC accumulators of the factored form (x K[i][j] at the end)
+  float acc[Q][Q];
+  const float dscale = A.dts ? as_const(A.dts)[tree] : 1.0f;
+  const float f = active ? dscale : 0.0f;
+  float gnext[Q];  // cotangent handed to the next reverse step; the root's first
+#pragma unroll
+  for (int i = 0; i < Q; ++i) gnext[i] = groot[i] * f;
+#pragma unroll
+  for (int i = 0; i < Q; ++i)
+#pragma unroll
+    for (int j = 0; j < Q; ++j) acc[i][j] = 0.0f;
+
+  // the DP rows a step re-reads are issued kAdjRing - 1 steps ahead, both
+  // loads unconditionally (a row the step does not read is addressed past the
+  // buffer: no traffic, zeros) so every path issues the same number of VMEM ops
+  auto pf_rows = [&](int k, float (&nd)[2][Q]) __attribute__((always_inline)) {
+    int r0 = kF4NoRow, r1 = kF4NoRow;
+    if (k >= 0) {
+      r0 = prog[kF4RecInts * k + 5];
+      r1 = prog[kF4RecInts * k + 6];
+    }
+    bld_row<Q, kAuxFusedLoad>(rdp, r0 >= 0 ? voff : 0x7FFFFFF0, max(r0, 0) * rowbytes, nd[0]);
+    bld_row<Q, kAuxFusedLoad>(rdp, r1 >= 0 ? voff : 0x7FFFFFF0, max(r1, 0) * rowbytes, nd[1]);
+  };
+  // acc_ij += g_i W[code][i][j] of a leaf child
+  auto leaf_acc = [&](const float (&g)[Q], const float (&w)[Q * Q]) __attribute__((always_inline)) {
+#pragma unroll
+    for (int i = 0; i < Q; ++i) {
+      float wr[Q];
+#pragma unroll
+      for (int j = 0; j < Q; ++j) wr[j] = w[i * Q + j];
+      axpy<Q>(acc[i], g[i], wr);
+    }
+  };
+  // edge to an internal child: its cotangent to the bypass or to its slot
+  auto int_child = [&](bool deferred, bool prev, int off, const float (&d)[Q],
+                       const float (&g)[Q]) __attribute__((always_inline)) {
+    float gc[Q];
+    if (deferred) {
+      // the child's step runs this edge (kF4DeferIn)
+#pragma unroll
+      for (int j = 0; j < Q; ++j) gc[j] = g[j];
+    } else {
+      message_adjoint<Q, MODE, SYM>(cf, a, d, g, acc, gc);
+    }
+    if (prev) {
+#pragma unroll
+      for (int j = 0; j < Q; ++j) gnext[j] = gc[j];
+    } else {
+      wr_slot(off, gc);
+    }
+  };
+  auto bstep = [&](const F4Rec& s, float (&cd)[2][Q]) __attribute__((always_inline)) {
+    const int fl = s.flags;
+    float g[Q];
+    if (fl & (kF4ToNext | kF4Root)) {
+#pragma unroll
+      for (int i = 0; i < Q; ++i) g[i] = gnext[i];
+    } else {
+      rd_slot(s.slot, g);
+    }
+    if (fl & kF4DeferIn) {
+      // g is the parent's cotangent: the parent -> cherry edge first.  Its u
+      // and 1 / s depend on the two leaf codes only (pair tables); both code
+      // reads go out together
+      const int c0 = rd_code(s.a0), c1 = rd_code(s.a1);
+      const int pair = c0 * (Q + 1) + c1;
+      float u[Q], rs[Q], gc[Q];
+      lds_vec_get<Q>(tu + pair * Q, u);
+      lds_vec_get<Q>(tr + pair * Q, rs);
+      softk_edge<Q>(cf, u, rs, g, acc, gc);
+#pragma unroll
+      for (int i = 0; i < Q; ++i) g[i] = gc[i];
+    }
+    // the children in stored order (the dC sums depend on it).  One loop for
+    // every class: straight-line code per class (a leaf's weights read beside
+    // the other child's edge, a cherry's two weight tables and its edge tables
+    // in one batch) measured 95 VGPRs or spills against 88 here, and the same
+    // time (PERFLOG.md)
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+      const int off = c == 0 ? s.a0 : s.a1;
+      if (fl & (c == 0 ? kF4Leaf0 : kF4Leaf1)) {
+        const int code = rd_code(off);
+        float w[Q * Q];
+        lds_vec_get<Q * Q>(tab + kWTab + code * Q * Q, w);
+        leaf_acc(g, w);
+      } else {
+        int_child((fl & (c == 0 ? kF4Defer0 : kF4Defer1)) != 0,
+                  (fl & (c == 0 ? kF4Prev0 : kF4Prev1)) != 0, off, cd[c], g);
+      }
+    }
+  };
+  {
+    // ring of kRing row buffers, unrolled so every buffer index is static;
+    // the step records themselves are read one step ahead
+    constexpr int kRing = kAdjRing;
+    float buf[kRing][2][Q];
+#pragma unroll
+    for (int r = 0; r < kRing - 1; ++r) pf_rows(n_int - 1 - r, buf[r]);
+    F4Rec nxt = load_rec(prog, n_int - 1);
+    for (int k = n_int - 1; k >= 0; k -= kRing) {
+#pragma unroll
+      for (int r = 0; r < kRing; ++r) {
+        // step k - r uses buf[r]; its freed predecessor takes the rows of
+        // step k - r - (kRing - 1)
+        pf_rows(k - r - (kRing - 1), buf[(r + kRing - 1) % kRing]);
+        if (k - r < 0) break;
+        const F4Rec s = nxt;
+        if (k - r - 1 >= 0) nxt = load_rec(prog, k - r - 1);
+        bstep(s, buf[r]);
+      }
+    }
+  }
+
+  // ---- per-item dC partial (the fixed-order reduce kernel sums the items) ----
+  double v16[16];
+#pragma unroll
+  for (int i = 0; i < Q; ++i)
+#pragma unroll
+    for (int j = 0; j < Q; ++j) {
+      v16[i * Q + j] = (double)acc[i][j];
+      v16[i * Q + j] *= (double)cf.k[i][j];
+    }
+  const double v = wave_reduce_scatter16(v16, lane);
+  if ((lane & 3) == 0) A.part_dc[(size_t)(lane >> 2) * nb + item] = v;
+}
+
+__global__ __launch_bounds__(kWave)
+__attribute__((amdgpu_waves_per_eu(kFusedWpe, kFusedWpeMax)))
+void sankoff_fused4_kernel(KArgs A, const int* prog) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  float cmin, cmax;
+  cost_range<4>(A.cost, cmin, cmax);
+  if (use_ktrick(cmin, cmax, A.a)) {
+    if (cost_symmetric<4>(A.cost))
+      fused4_body<true>(A, prog, lds);
+    else
+      fused4_body<false>(A, prog, lds);
+  } else {
+    sankoff_body<4, kSoftDirect, 3, false>(A, lds);
+  }
+}
+
+}  // namespace
+
+int g_fused4_launches = 0;  // tests: which kernel took a call
+
+bool fused4_enabled() {
+  const char* e = std::getenv("TREX_FUSED4");  // read per call (tests run both kernels)
+  return !(e && e[0] == '0');
+}
+
+int fused4_run(const char* fn, const void* kargs, size_t kargs_bytes, const int32_t* prog,
+               size_t lds, void* stream) {
+  KArgs A;
+  if (kargs_bytes != sizeof(A))
+    return set_error(TREX_E_ARG, "%s: kernel argument size mismatch", fn);
+  std::memcpy(&A, kargs, sizeof(A));
+  const int grid = (A.nblocks + 7) / 8 * 8;
+  hipLaunchKernelGGL(sankoff_fused4_kernel, dim3(grid), dim3(kWave), lds, (hipStream_t)stream, A,
+                     reinterpret_cast<const int*>(prog + TREX_PLAN_HEADER_INTS));
+  ++g_fused4_launches;
+  return hip_check(fn);
+}
+
+}  // namespace trex
+
+extern "C" int trex_debug_fused4_launches(void) { return trex::g_fused4_launches; }

@@ -59,6 +59,47 @@ constexpr int kKindInline = 3;
 inline int64_t lp_steps_offset(int ni) { return 8 + (((int64_t)ni + 1 + 3) & ~3LL); }
 inline int64_t lp_tree_ints(int ni) { return lp_steps_offset(ni) + 4LL * ni; }
 
+// Fused Q = 4 program (trex_fused4_program_build, plan.cpp; run by
+// sankoff_fused4.hip): the plan's forward steps decoded once on the host, so
+// the kernel's loops read operands instead of decoding descriptors.  Layout
+// (ints): header [TREX_PLAN_HEADER_INTS] = {kF4Magic, B, n_all, n_int, 0...}
+// | records [B][n_int][kF4RecInts], tree by tree in the plan's step order.
+// Record (32 bytes, one scalar load):
+//   [0] flags: the kF4* bits below | forward class << 16
+//   [1] DP row of the step's node
+//   [2] [3] operand of child 0 / child 1 (stored order), an LDS byte offset:
+//       leaf child: leaf index * 64 into the leaf tile (+ lane);
+//       internal child: slot * 1024 into the slot stack (+ lane * 16), 0 when
+//       the child is the previous step (kF4Prev*, register bypass)
+//   [4] the node's own slot * 1024 (forward sink when kF4Put, reverse
+//       cotangent source unless kF4ToNext / kF4Root); 0 when it has none
+//   [5] [6] DP row of child 0 / child 1 that the adjoint re-reads, or
+//       kF4NoRow (leaf child, deferred cherry: nothing is read)
+//   [7] 0
+// Forward classes: kF4Cherry both children leaves; kF4CherryDeferred the same
+// with the parent edge deferred to this step (kStepDeferredIn: pair tables);
+// kF4LeafInt one leaf and one internal child (kF4Leaf0 tells which: the sum
+// of the two messages commutes); kF4IntInt.  The reverse sweep runs the
+// children in stored order off the flag bits (the dC sums depend on the order).
+constexpr int32_t kF4Magic = 0x54524634;  // 'TRF4'
+constexpr int kF4RecInts = 8;
+constexpr int32_t kF4Leaf0 = 1, kF4Leaf1 = 2;    // child 0 / 1 is a leaf
+constexpr int32_t kF4Prev0 = 4, kF4Prev1 = 8;    // kChildPrev of child 0 / 1
+constexpr int32_t kF4Defer0 = 16, kF4Defer1 = 32;  // kChildDeferred of child 0 / 1
+constexpr int32_t kF4DeferIn = 64;               // kStepDeferredIn
+constexpr int32_t kF4ToNext = 128;               // kStepToNext
+constexpr int32_t kF4Root = 256;                 // kStepRoot
+constexpr int32_t kF4Put = 512;                  // the forward writes the node's slot
+constexpr int kF4Cherry = 0, kF4CherryDeferred = 1, kF4LeafInt = 2, kF4IntInt = 3;
+constexpr int kF4FwdClassShift = 16;
+constexpr int32_t kF4NoRow = -1;
+// launches the fused Q = 4 kernel on a call run_phase (sankoff.hip) found in
+// scope; kargs: its KArgs (the kernels' argument struct is private to each
+// translation unit, hence the bytes), prog: the device copy of the program
+bool fused4_enabled();  // TREX_FUSED4 != "0" (read per call)
+int fused4_run(const char* fn, const void* kargs, size_t kargs_bytes, const int32_t* prog,
+               size_t lds, void* stream);
+
 // backtrack entry kinds (bits 16-19 of word 0)
 constexpr int kBtRoot = 0;
 constexpr int kBtReal = 1;

@@ -81,6 +81,27 @@ class SankoffEngine:
         self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         # arrival counters of the in-kernel reductions start at zero
         check(lib().trex_workspace_init(ptr(self.workspace), nbytes, stream_handle(self.device)))
+        # Q = 4: the plan's steps predecoded for the fused softmin kernel
+        # (sankoff_fused4.hip), built and uploaded once; None when the planner
+        # refuses the topology (the generic kernel then takes every call)
+        self.fused4_prog = self._fused4_program() if self.Q == 4 else None
+
+    def _fused4_program(self):
+        from ._lib import TREX_E_UNSUPPORTED, has_fused4
+
+        L = lib()
+        if not has_fused4():
+            return None
+        p = self.plan
+        n = L.trex_fused4_program_ints(p.B, p.n_all)
+        if n <= 0:
+            return None
+        host = np.zeros(n, dtype=np.int32)
+        rc = L.trex_fused4_program_build(p.host.ctypes.data, p.B, p.n_all, host.ctypes.data)
+        if rc == TREX_E_UNSUPPORTED:
+            return None
+        check(rc)
+        return _torch().from_numpy(host).to(self.device)
 
     @staticmethod
     def _flags(hard_root):
@@ -210,11 +231,14 @@ class SankoffEngine:
             if d_tree_score.shape != (p.B,):
                 raise ValueError("d_tree_score must be (B,)")
         flags = self._flags(hard_root)
-        check(lib().trex_sankoff_fwd_bwd(
-            ptr(self.plan_dev), p.slot_word, ptr(leaves), ptr(cost), p.B, self.L, p.n_all,
-            self.Q, float(tau), flags, ptr(dp_t), ptr(ss), ptr(ts), ptr(d_tree_score), ptr(dc),
-            ptr(mg), ptr(an), ptr(self.workspace), self.workspace.numel(),
-            stream_handle(self.device)))
+        args = (ptr(self.plan_dev), p.slot_word, ptr(leaves), ptr(cost), p.B, self.L, p.n_all,
+                self.Q, float(tau), flags, ptr(dp_t), ptr(ss), ptr(ts), ptr(d_tree_score), ptr(dc),
+                ptr(mg), ptr(an), ptr(self.workspace), self.workspace.numel(),
+                stream_handle(self.device))
+        if self.fused4_prog is not None:
+            check(lib().trex_sankoff_fwd_bwd_prog(*args, ptr(self.fused4_prog)))
+        else:
+            check(lib().trex_sankoff_fwd_bwd(*args))
         return ForwardResult(ts, dp_t, ss), dc, mg, an
 
     def backtrack(self, cost, dp):
