@@ -13,7 +13,6 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstdlib>
 #include <mutex>
 
 #include "sankoff_dev.h"
@@ -22,9 +21,33 @@
 
 namespace trex {
 
-namespace {
+static thread_local char g_err[512] = "no error";
 
-thread_local char g_err[512] = "no error";
+int set_error(int code, const char* fmt, ...) {
+  va_list ap;
+  va_start(ap, fmt);
+  std::vsnprintf(g_err, sizeof(g_err), fmt, ap);
+  va_end(ap);
+  return code;
+}
+
+int hip_check(const char* fn) {
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return set_error(TREX_E_HIP, "%s: %s", fn, hipGetErrorString(e));
+  return TREX_OK;
+}
+
+void tau_coefs(float tau, float* a, float* bcoef) {
+  if (tau > 0.0f) {
+    *a = (float)(1.4426950408889634 / (double)tau);
+    *bcoef = (float)((double)tau * 0.6931471805599453);
+  } else {
+    *a = 0.0f;
+    *bcoef = 0.0f;
+  }
+}
+
+namespace {
 
 template <int Q, bool SOFT, int PHASE, bool RAGGED = false>
 __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(
@@ -173,8 +196,6 @@ int check_shape(const char* fn, int B, int L, int n_all, int Q, Shape* sh) {
   return TREX_OK;
 }
 
-int tiles_for(int L) { return (L + kWave - 1) / kWave; }
-
 size_t lds_bytes(int n_slots, int nl, int Q, int phase) {
   const size_t b = (size_t)tab_floats(phase) * 4 +
                    (size_t)std::max(n_slots, 1) * Q * kWave * 4 + (size_t)nl * kWave;
@@ -192,26 +213,17 @@ int device_cus() {
   return cus;
 }
 
-int64_t counters_bytes(int B) { return ((int64_t)4 * (B + 1) + 255) / 256 * 256; }
-
 // persistent grid: as many single-wave blocks as are co-resident (occupancy
 // x CUs), a multiple of 8 (one share per XCD), never more than the items
 template <class K>
 int persistent_grid(K kernel, size_t lds, int nitems) {
   static std::mutex mu;
-  static int cus = 0;
   struct Entry { const void* k; size_t lds; int occ; };
   static Entry cache[64];
   static int ncache = 0;
   int occ = 0;
   {
     std::lock_guard<std::mutex> g(mu);
-    if (cus == 0) {
-      int dev = 0;
-      (void)hipGetDevice(&dev);
-      if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-        cus = 256;
-    }
     for (int i = 0; i < ncache; ++i)
       if (cache[i].k == (const void*)kernel && cache[i].lds == lds) occ = cache[i].occ;
     if (occ == 0) {
@@ -221,7 +233,7 @@ int persistent_grid(K kernel, size_t lds, int nitems) {
       if (ncache < 64) cache[ncache++] = Entry{(const void*)kernel, lds, occ};
     }
   }
-  const long resident = (long)cus * occ / 8 * 8;
+  const long resident = (long)device_cus() * occ / 8 * 8;
   const long want = ((long)nitems + 7) / 8 * 8;
   return (int)std::max(8L, std::min(resident, want));
 }
@@ -230,16 +242,11 @@ int persistent_grid(K kernel, size_t lds, int nitems) {
 // grid measured
 template <int Q, bool SOFT, bool RAGGED>
 void launch_phase(int phase, size_t lds, hipStream_t st, const KArgs& A) {
-  auto go = [&](auto kernel) {
+  with_phase(phase, [&](auto P) {
+    auto kernel = sankoff_kernel<Q, SOFT, decltype(P)::value, RAGGED>;
     const int grid = phase == 1 ? persistent_grid(kernel, lds, A.nblocks) : (A.nblocks + 7) / 8 * 8;
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(kWave), lds, st, A);
-  };
-  if (phase == 1)
-    go(sankoff_kernel<Q, SOFT, 1, RAGGED>);
-  else if (phase == 2)
-    go(sankoff_kernel<Q, SOFT, 2, RAGGED>);
-  else
-    go(sankoff_kernel<Q, SOFT, 3, RAGGED>);
+  });
 }
 
 template <bool RAGGED>
@@ -260,78 +267,14 @@ void launch_q(int Q, int phase, bool soft, size_t lds, hipStream_t st, const KAr
   }
 }
 
-// common entry: validates, fills KArgs, launches one phase
-// Q <= 4 on a small grid (few trees x few sites: C2 is one tree, 157 waves
-// of 64 sites for 1 024 SIMDs) runs the state-parallel kernel instead: 4
-// lanes per site (one per parent state), 16 sites per wave, 4x the waves and
-// a quarter of the per-lane work on the serial node chain.
-// TREX_WIDE_SMALLQ=0 / 1 forces the choice (A/B).
-bool wide_small_q(int B, int L, int Q) {
-  if (Q > 4) return false;
-  // read per call (tests run both kernels in one process)
-  const char* e = std::getenv("TREX_WIDE_SMALLQ");
-  if (e && (e[0] == '0' || e[0] == '1')) return e[0] == '1';
-  // up to ~1.5 64-site waves per CU on the lane-per-site kernel (measured
-  // on 256 CUs, 32-taxa trees x 5 000 sites: 158 waves 43.8 -> 40.4 us, 316
-  // waves 46.5 -> 44.9 us, 632 waves 48.2 vs 51.8 us (lane-per-site wins);
-  // C2 71 -> 67 us; a C4 shard, 10 000 waves, is 2.2x slower
-  // state-parallel).  Scaled by the CU count (a CPX partition has 32 CUs).
-  return (int64_t)B * ((L + kWave - 1) / kWave) * 2 <= (int64_t)3 * device_cus();
-}
-
-// Grids of at most about one state-parallel wave per SIMD (C2: one tree x
-// 625 16-site items) run the staged kernel (sankoff_staged.hip): one
-// workgroup of waves per item, the tree's levels spread over the waves, so
-// the serial chain is the tree height instead of every internal node.
-// TREX_STAGED=0 / 1 forces it off / on (whenever its LDS fits; A/B, tests).
-bool use_staged(int B, int L, int Q, int ni, int nl, int phase) {
-  if (staged_lds_bytes(ni, nl, Q, phase) > kLdsPerCu) return false;
-  const char* e = std::getenv("TREX_STAGED");  // read per call (tests flip it)
-  if (e && (e[0] == '0' || e[0] == '1')) return e[0] == '1';
-  return (int64_t)B * wide_tiles(L, Q) <= (int64_t)4 * device_cus();
-}
-
-int run_phase(const char* fn, int phase, const int32_t* plan, int n_slots, const int8_t* leaves,
-              const float* cost, int B, int L, int n_all, int Q, float tau, unsigned flags,
-              float* dp, float* site_score, float* tree_score, const float* dts, float* d_cost,
-              float* marg, int8_t* anc, void* workspace, int64_t workspace_bytes, void* stream,
-              const int32_t* prog = nullptr);
-
-}  // namespace
-
-int set_error(int code, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  std::vsnprintf(g_err, sizeof(g_err), fmt, ap);
-  va_end(ap);
-  return code;
-}
-
-int hip_check(const char* fn) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return set_error(TREX_E_HIP, "%s: %s", fn, hipGetErrorString(e));
-  return TREX_OK;
-}
-
-void tau_coefs(float tau, float* a, float* bcoef) {
-  if (tau > 0.0f) {
-    *a = (float)(1.4426950408889634 / (double)tau);
-    *bcoef = (float)((double)tau * 0.6931471805599453);
-  } else {
-    *a = 0.0f;
-    *bcoef = 0.0f;
-  }
-}
-
-namespace {
-
-// the entry points' arguments as the other kernels' host code takes them; a
-// ragged call passes L = 0 and the largest tree's nl / ni
-WideCall wide_call(int phase, const int* steps, const int8_t* leaves, const float* cost, int B,
-                   int L, int nl, int ni, int Q, int n_slots, float tau, unsigned flags, float* dp,
-                   float* site_score, float* tree_score, const float* dts, float* d_cost,
-                   float* marg, int8_t* anc, void* workspace, void* stream) {
-  WideCall c;
+// the call record of an entry point's arguments; a ragged call passes L = 0
+// and the largest tree's nl / ni, and sets rmeta / ritem / items itself
+SankoffCall sankoff_call(int phase, const int* steps, const int8_t* leaves, const float* cost,
+                         int B, int L, int nl, int ni, int Q, int n_slots, float tau,
+                         unsigned flags, float* dp, float* site_score, float* tree_score,
+                         const float* dts, float* d_cost, float* marg, int8_t* anc,
+                         void* workspace, void* stream) {
+  SankoffCall c;
   c.phase = phase;
   c.soft = tau > 0.0f;
   c.steps = steps;
@@ -357,46 +300,127 @@ WideCall wide_call(int phase, const int* steps, const int8_t* leaves, const floa
   return c;
 }
 
-// the Q <= 4 kernel's arguments of a uniform batch of B trees of n_int rows,
-// L sites and tiles items each, or (n_int = L = tiles = 0; the caller sets
-// rmeta / ritem) of a ragged one; part: the nblocks per-item score partials,
-// then the [Q*Q][nblocks] dC partials
-KArgs kargs(const int* steps, const int8_t* leaves, const float* cost, int n_int, int nl, int L,
-            int tiles, int B, int n_slots, float tau, unsigned flags, float* dp, float* site_score,
-            float* tree_score, const float* dts, float* d_cost, float* marg, int8_t* anc,
-            void* part, int nblocks) {
-  KArgs A;
-  A.steps = reinterpret_cast<const int4*>(steps);
-  A.leaves = leaves;
-  A.cost = cost;
-  A.n_int = n_int;
-  A.nl = nl;
-  A.L = L;
-  A.tiles = tiles;
-  A.B = B;
-  A.n_slots = n_slots;
-  tau_coefs(tau, &A.a, &A.bcoef);
-  A.hard_root = (flags & TREX_FLAG_HARD_ROOT) ? 1 : 0;
-  A.dp = dp;
-  A.site_score = site_score;
-  A.tree_score = tree_score;
-  A.dts = dts;
-  A.marg = marg;
-  A.anc = anc;
-  A.d_cost = d_cost;
-  A.part_tree = static_cast<double*>(part);
-  A.part_dc = A.part_tree + nblocks;
-  A.nblocks = nblocks;
-  A.rmeta = nullptr;
-  A.ritem = nullptr;
-  return A;
+// --------------------------------------------------------------------------
+// routing: which kernel family takes a call
+// --------------------------------------------------------------------------
+// Q <= 4 on a small grid (few trees x few sites: C2 is one tree, 157 waves
+// of 64 sites for 1 024 SIMDs) runs the state-parallel kernel instead: 4
+// lanes per site (one per parent state), 16 sites per wave, 4x the waves and
+// a quarter of the per-lane work on the serial node chain.
+// TREX_WIDE_SMALLQ=0 / 1 forces the choice (A/B).
+bool wide_small_q(int B, int L, int Q) {
+  if (Q > 4) return false;
+  const int forced = env_switch("TREX_WIDE_SMALLQ");
+  if (forced >= 0) return forced;
+  // up to ~1.5 64-site waves per CU on the lane-per-site kernel (measured
+  // on 256 CUs, 32-taxa trees x 5 000 sites: 158 waves 43.8 -> 40.4 us, 316
+  // waves 46.5 -> 44.9 us, 632 waves 48.2 vs 51.8 us (lane-per-site wins);
+  // C2 71 -> 67 us; a C4 shard, 10 000 waves, is 2.2x slower
+  // state-parallel).  Scaled by the CU count (a CPX partition has 32 CUs).
+  return (int64_t)B * q4_tiles(L) * 2 <= (int64_t)3 * device_cus();
 }
 
+// Grids of at most about one state-parallel wave per SIMD (C2: one tree x
+// 625 16-site items) run the staged kernel (sankoff_staged.hip): one
+// workgroup of waves per item, the tree's levels spread over the waves, so
+// the serial chain is the tree height instead of every internal node.
+// TREX_STAGED=0 / 1 forces it off / on (whenever its LDS fits; A/B, tests).
+bool use_staged(const SankoffCall& c) {
+  if (staged_lds_bytes(c.ni, c.nl, c.Q, c.phase) > kLdsPerCu) return false;
+  const int forced = env_switch("TREX_STAGED");
+  if (forced >= 0) return forced;
+  return (int64_t)c.B * wide_tiles(c.L, c.Q) <= (int64_t)4 * device_cus();
+}
+
+enum class Family { kBigq, kSite, kSite2, kStaged, kWide, kQ4, kFused4 };
+
+struct Route {
+  Family family;
+  int lp_slots = -1;  // slots of the plan's lane programs (-1: a tree has none)
+  // kSite / kSite2: the gate's flag and K / K^T in the wide workspace's tail,
+  // and whether the fused kernel keeps its s rows (phase 3, the workspace
+  // has room for them, TREX_SITE_SROW is not 0)
+  int* site_flag = nullptr;
+  float* site_kg = nullptr;
+  bool keep_srow = false;
+};
+
+// Pure: reads the call, the plan's slot word (info[0]: stack depth |
+// (lane-program slots + 1) << 16), whether the caller passed a fused Q = 4
+// program, the workspace size and the TREX_* knobs (per call: the tests flip
+// them inside one process).
+Route route(const SankoffCall& c, int slot_word, bool has_prog, int64_t workspace_bytes) {
+  Route r;
+  if (c.rmeta) {
+    // ragged: protein / codon alphabets on the state-parallel kernel, each
+    // 64-site item split over ceil(64 / sites-per-wave) waves
+    r.family = c.Q > kWideMaxQ ? Family::kBigq : c.Q > 4 ? Family::kWide : Family::kQ4;
+    return r;
+  }
+  r.lp_slots = ((slot_word >> 16) & 0xFF) - 1;
+  if (c.Q > 4 || wide_small_q(c.B, c.L, c.Q)) {
+    if (c.Q > kWideMaxQ) {
+      r.family = Family::kBigq;  // 64 < Q <= 128 (sankoff_bigq.hip)
+    } else if (site_eligible(c, r.lp_slots)) {
+      // the lane-per-site kernel (sankoff_site.hip) takes the call when the
+      // cost matrix allows the factored softmin -- decided on the device: the
+      // state-parallel kernel runs first, gated (every workgroup checks the
+      // cost range and exits when the site kernel takes the call; workgroup
+      // 0 writes K, K^T and the flag into the workspace tail), then the site
+      // kernel (exits unless the flag is set), then one reduce that sums
+      // whichever kernel's partials the flag names
+      char* tail = static_cast<char*>(c.workspace) + wide_workspace_bytes(c.B, c.L, c.Q);
+      r.site_flag = reinterpret_cast<int*>(tail - kWideTailFlag);
+      r.site_kg = reinterpret_cast<float*>(tail - kWideTailKg);
+      // the kept s rows are optional: a workspace without them
+      // (site_srow_offset bytes) makes the adjoint recompute them
+      r.keep_srow = c.phase == 3 &&
+                    workspace_bytes >= trex_workspace_bytes(c.B, c.L, c.nl + c.ni, c.Q) &&
+                    env_switch("TREX_SITE_SROW") != 0;
+      r.family = site2_on(r.lp_slots, c.nl, c.ni) ? Family::kSite2 : Family::kSite;
+    } else {
+      r.family = use_staged(c) ? Family::kStaged : Family::kWide;
+    }
+    return r;
+  }
+  // the fused Q = 4 softmin kernel on the predecoded program (sankoff_fused4.hip)
+  // takes the calls in its scope; same partials, same reduce
+  const bool fused4 = has_prog && c.phase == 3 && c.Q == 4 && c.soft && !c.site_score &&
+                      !c.marg && !c.anc && (c.L & 3) == 0 && c.nl <= kPrefetchRows &&
+                      env_switch("TREX_FUSED4") != 0;
+  r.family = fused4 ? Family::kFused4 : Family::kQ4;
+  return r;
+}
+
+// the lane-per-site Q <= 4 kernel (prog: the fused Q = 4 one on that program),
+// then the reduce of its per-item partials
+int q4_run(const char* fn, const SankoffCall& c, const int32_t* prog = nullptr) {
+  if ((int64_t)c.ni * c.L * c.Q * 4 > 0x7FFFFFF0LL)
+    return set_error(TREX_E_UNSUPPORTED, "%s: one tree's DP table exceeds 2 GiB", fn);
+  const size_t lds = lds_bytes(c.n_slots, c.nl, c.Q, c.phase);
+  if (lds > 65536) return set_error(TREX_E_UNSUPPORTED, "%s: LDS stack too deep", fn);
+  if ((int64_t)c.B * q4_tiles(c.L) > 0x7FFFFFFF)
+    return set_error(TREX_E_ARG, "%s: grid too large", fn);
+  const KArgs A = q4_args(c);
+  if (prog) {
+    if (int e = fused4_run(fn, c, prog, lds)) return e;
+  } else {
+    if (!c.rmeta)
+      launch_q<false>(c.Q, c.phase, c.soft, lds, (hipStream_t)c.stream, A);
+    else
+      launch_q<true>(c.Q, c.phase, c.soft, lds, (hipStream_t)c.stream, A);
+    if (int e = hip_check(fn)) return e;
+  }
+  const RaggedParts rp = ragged_parts(c);
+  return partial_reduce(fn, c, A.part_tree, A.part_dc, A.tiles, c.rmeta ? &rp : nullptr);
+}
+
+// common entry: validates, builds the call, routes it, launches one phase
 int run_phase(const char* fn, int phase, const int32_t* plan, int n_slots, const int8_t* leaves,
               const float* cost, int B, int L, int n_all, int Q, float tau, unsigned flags,
               float* dp, float* site_score, float* tree_score, const float* dts, float* d_cost,
               float* marg, int8_t* anc, void* workspace, int64_t workspace_bytes, void* stream,
-              const int32_t* prog) {
+              const int32_t* prog = nullptr) {
   Shape s;
   if (int e = check_shape(fn, B, L, n_all, Q, &s)) return e;
   if (!plan || !leaves || !cost || !workspace)
@@ -406,74 +430,42 @@ int run_phase(const char* fn, int phase, const int32_t* plan, int n_slots, const
     return set_error(TREX_E_ARG, "%s: dp and d_cost are required", fn);
   if (!nonneg_finite_f32(tau))
     return set_error(TREX_E_ARG, "%s: tau must be finite and >= 0 (got %g)", fn, tau);
-  // 4 < Q <= 20: the kept s rows of the fused site kernel are optional -- a
-  // workspace without them (site_srow_offset bytes) makes it recompute them
-  const bool srow_room = workspace_bytes >= trex_workspace_bytes(B, L, n_all, Q);
+  // 4 < Q <= 20: the kept s rows of the fused site kernel are optional
   const int64_t min_ws = (Q > 4 && Q <= kSiteMaxQ) ? site_srow_offset(B, L, Q)
                                                    : trex_workspace_bytes(B, L, n_all, Q);
   if (workspace_bytes < min_ws) return set_error(TREX_E_ARG, "%s: workspace too small", fn);
   if (n_slots < 0) return set_error(TREX_E_ARG, "%s: bad n_slots", fn);
   if (flags & ~TREX_FLAG_HARD_ROOT) return set_error(TREX_E_ARG, "%s: unknown flags 0x%x", fn, flags);
-  // plan info[0]: stack depth | (lane-program slots + 1) << 16
-  const int lp_slots = ((n_slots >> 16) & 0xFF) - 1;
-  n_slots &= 0xFFFF;
-  if (n_slots > 250) return set_error(TREX_E_ARG, "%s: bad n_slots", fn);
-  if (Q > 4 || wide_small_q(B, L, Q)) {
-    WideCall c = wide_call(phase, plan + TREX_PLAN_HEADER_INTS, leaves, cost, B, L, s.nl, s.ni, Q,
-                           n_slots, tau, flags, dp, site_score, tree_score, dts, d_cost, marg, anc,
-                           workspace, stream);
-    if (Q > kWideMaxQ) return bigq_run(fn, c);  // 64 < Q <= 128 (sankoff_bigq.hip)
-    const int32_t* staged = plan + TREX_PLAN_HEADER_INTS + (int64_t)B * s.ni * 6;
-    const int32_t* lanes = staged + (int64_t)B * staged_tree_ints(s.ni);
-    if (site_eligible(c, lp_slots)) {
-      // the lane-per-site kernel (sankoff_site.hip) takes the call when the
-      // cost matrix allows the factored softmin -- decided on the device: the
-      // state-parallel kernel runs first, gated (every workgroup checks the
-      // cost range and exits when the site kernel takes the call; workgroup
-      // 0 writes K, K^T and the flag into the workspace tail), then the site
-      // kernel (exits unless the flag is set), then one reduce that sums
-      // whichever kernel's partials the flag names
-      char* tail = static_cast<char*>(workspace) + wide_workspace_bytes(B, L, Q);
-      int* flag = reinterpret_cast<int*>(tail - 128);
-      float* kg = reinterpret_cast<float*>(tail - 3456);  // K and K^T
-      c.site_flag = flag;
-      c.site_kg = kg;
-      if (phase == 3 && srow_room && site_srow_on())
-        c.site_srow = reinterpret_cast<float*>(static_cast<char*>(workspace) +
-                                               site_srow_offset(B, L, Q));
-      if (int e = wide_run(fn, c, /*reduce=*/false)) return e;
-      if (int e = site2_on(lp_slots, c.nl, c.ni) ? site2_run(fn, c, lanes, lp_slots, flag, kg)
-                                                 : site_run(fn, c, lanes, lp_slots, flag, kg))
-        return e;
-      return partial_reduce(fn, static_cast<double*>(workspace),
-                            static_cast<double*>(workspace) + (int64_t)B * wide_tiles(L, Q), B,
-                            wide_tiles(L, Q), Q, phase, tree_score, d_cost, stream, nullptr, 0, 0,
-                            1, flag, site_tiles(L));
-    }
-    if (use_staged(B, L, Q, s.ni, s.nl, phase)) return staged_run(fn, c, staged);
-    return wide_run(fn, c);
+  // n_slots is the plan's slot word: the stack depth in its low half (route)
+  if ((n_slots & 0xFFFF) > 250) return set_error(TREX_E_ARG, "%s: bad n_slots", fn);
+  SankoffCall c = sankoff_call(phase, plan + TREX_PLAN_HEADER_INTS, leaves, cost, B, L, s.nl, s.ni,
+                               Q, n_slots & 0xFFFF, tau, flags, dp, site_score, tree_score, dts,
+                               d_cost, marg, anc, workspace, stream);
+  const Route r = route(c, n_slots, prog != nullptr, workspace_bytes);
+  const int32_t* staged = plan + TREX_PLAN_HEADER_INTS + (int64_t)B * s.ni * 6;
+  const int32_t* lanes = staged + (int64_t)B * staged_tree_ints(s.ni);
+  switch (r.family) {
+    case Family::kBigq: return bigq_run(fn, c);
+    case Family::kStaged: return staged_run(fn, c, staged);
+    case Family::kWide: return wide_run(fn, c);
+    case Family::kQ4: return q4_run(fn, c);
+    case Family::kFused4: return q4_run(fn, c, prog);
+    case Family::kSite:
+    case Family::kSite2: break;
   }
-  if ((int64_t)s.ni * L * Q * 4 > 0x7FFFFFF0LL)
-    return set_error(TREX_E_UNSUPPORTED, "%s: one tree's DP table exceeds 2 GiB", fn);
-  const int tiles = tiles_for(L);
-  const size_t lds = lds_bytes(n_slots, s.nl, Q, phase);
-  if (lds > 65536) return set_error(TREX_E_UNSUPPORTED, "%s: LDS stack too deep", fn);
-  if ((int64_t)B * tiles > 0x7FFFFFFF) return set_error(TREX_E_ARG, "%s: grid too large", fn);
-  // workspace: per-item partials [B*tiles] + [Q*Q][B*tiles] doubles
-  const KArgs A = kargs(plan + TREX_PLAN_HEADER_INTS, leaves, cost, s.ni, s.nl, L, tiles, B,
-                        n_slots, tau, flags, dp, site_score, tree_score, dts, d_cost, marg, anc,
-                        static_cast<char*>(workspace) + counters_bytes(B), B * tiles);
-  // the fused Q = 4 softmin kernel on the predecoded program (sankoff_fused4.hip)
-  // takes the calls in its scope; same partials, same reduce
-  const bool fused4 = prog && phase == 3 && Q == 4 && tau > 0.0f && !site_score && !marg && !anc &&
-                      (L & 3) == 0 && s.nl <= kPrefetchRows && fused4_enabled();
-  if (fused4) {
-    if (int e = fused4_run(fn, &A, sizeof(A), prog, lds, stream)) return e;
-  } else {
-    launch_q<false>(Q, phase, tau > 0.0f, lds, (hipStream_t)stream, A);
-    if (int e = hip_check(fn)) return e;
-  }
-  return partial_reduce(fn, A.part_tree, A.part_dc, B, tiles, Q, phase, tree_score, d_cost, stream);
+  c.site_flag = r.site_flag;
+  c.site_kg = r.site_kg;
+  if (r.keep_srow)
+    c.site_srow = reinterpret_cast<float*>(static_cast<char*>(workspace) + site_srow_offset(B, L, Q));
+  if (int e = wide_run(fn, c, /*reduce=*/false)) return e;
+  if (int e = r.family == Family::kSite2 ? site2_run(fn, c, lanes, r.lp_slots)
+                                         : site_run(fn, c, lanes, r.lp_slots))
+    return e;
+  c.mx_flag = r.site_flag;
+  c.mx_tiles = site_tiles(L);
+  const int tiles = wide_tiles(L, Q);
+  const double* part = static_cast<const double*>(workspace);
+  return partial_reduce(fn, c, part, part + (int64_t)B * tiles, tiles);
 }
 
 }  // namespace
@@ -499,8 +491,8 @@ extern "C" int64_t trex_workspace_bytes(int B, int L, int n_all, int Q) {
     const int64_t ni = n_all - (n_all + 1) / 2;
     return site_srow_offset(B, L, Q) + (int64_t)B * std::max<int64_t>(ni, 0) * L * Q * 4;
   }
-  const int64_t nb = (int64_t)B * tiles_for(L);
-  const int64_t narrow = counters_bytes(B) + nb * 8 * (1 + (int64_t)Q * Q) + (int64_t)Q * Q * B * 8 + 256;
+  const int64_t nb = (int64_t)B * q4_tiles(L);
+  const int64_t narrow = q4_counters_bytes(B) + nb * 8 * (1 + (int64_t)Q * Q) + (int64_t)Q * Q * B * 8 + 256;
   // small grids may run the state-parallel wide kernel (G = 4): room for both
   return std::max<int64_t>(narrow, wide_workspace_bytes(B, L, Q));
 }
@@ -630,26 +622,17 @@ extern "C" int trex_sankoff_ragged(int phase, const int32_t* plan, int B, int n_
   // the plan: per-tree records, the work-item -> tree table, the steps
   const int* meta = plan + TREX_PLAN_HEADER_INTS;
   const int* ritem = meta + (size_t)B * kRaggedMeta;
-  const int* steps = ritem + items;
-  if (Q > 4) {
-    // protein / codon alphabets: the state-parallel kernel, each 64-site
-    // item split over ceil(64 / sites-per-wave) waves
-    const WideCall c = wide_call(phase, steps, leaves, cost, B, 0, max_nl, max_nl - 1, Q, n_slots,
-                                 tau, flags, dp, site_score, tree_score, d_tree_score, d_cost,
-                                 marginals, anc_states, workspace, stream);
-    if (Q > kWideMaxQ) return bigq_ragged_run(fn, c, meta, ritem, items);
-    return wide_ragged_run(fn, c, meta, ritem, items);
+  SankoffCall c = sankoff_call(phase, ritem + items, leaves, cost, B, 0, max_nl, max_nl - 1, Q,
+                               n_slots, tau, flags, dp, site_score, tree_score, d_tree_score,
+                               d_cost, marginals, anc_states, workspace, stream);
+  c.rmeta = meta;
+  c.ritem = ritem;
+  c.items = items;
+  switch (route(c, n_slots, false, workspace_bytes).family) {
+    case Family::kBigq: return bigq_run(fn, c);
+    case Family::kWide: return wide_ragged_run(fn, c);
+    default: return q4_run(fn, c);
   }
-  const size_t lds = lds_bytes(n_slots, max_nl, Q, phase);
-  if (lds > 65536) return set_error(TREX_E_UNSUPPORTED, "%s: LDS stack too deep", fn);
-  KArgs A = kargs(steps, leaves, cost, 0, max_nl, 0, 0, B, n_slots, tau, flags, dp, site_score,
-                  tree_score, d_tree_score, d_cost, marginals, anc_states, workspace, (int)items);
-  A.rmeta = meta;
-  A.ritem = ritem;
-  launch_q<true>(Q, phase, tau > 0.0f, lds, (hipStream_t)stream, A);
-  if (int e = hip_check(fn)) return e;
-  return partial_reduce(fn, A.part_tree, A.part_dc, B, 0, Q, phase, tree_score, d_cost, stream,
-                        meta + 5, kRaggedMeta, (int)items);
 }
 
 extern "C" int trex_sankoff_ragged_backtrack(const int32_t* plan, int B, int64_t items,

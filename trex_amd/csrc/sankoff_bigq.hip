@@ -396,97 +396,43 @@ size_t bigq_lds_bytes(int n_slots, int Q) {
 }
 
 template <bool RAGGED>
-int bigq_launch(const char* fn, const BigArgs& A, const WideCall& c, int64_t nb, size_t lds) {
+int bigq_launch(const char* fn, const BigArgs& A, const SankoffCall& c, int64_t nb, size_t lds) {
   hipStream_t st = (hipStream_t)c.stream;
   auto go = [&](auto kernel) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL(kernel, dim3((unsigned)nb), dim3(kBigThreads), lds, st, A);
   };
-  if (c.soft) {
-    if (c.phase == 1) go(sankoff_bigq_kernel<1, true, RAGGED>);
-    else if (c.phase == 2) go(sankoff_bigq_kernel<2, true, RAGGED>);
-    else go(sankoff_bigq_kernel<3, true, RAGGED>);
-  } else {
-    if (c.phase == 1) go(sankoff_bigq_kernel<1, false, RAGGED>);
-    else if (c.phase == 2) go(sankoff_bigq_kernel<2, false, RAGGED>);
-    else go(sankoff_bigq_kernel<3, false, RAGGED>);
-  }
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return set_error(TREX_E_HIP, "%s: %s", fn, hipGetErrorString(e));
-  return TREX_OK;
+  if (c.soft)
+    with_phase(c.phase, [&](auto P) { go(sankoff_bigq_kernel<decltype(P)::value, true, RAGGED>); });
+  else
+    with_phase(c.phase, [&](auto P) { go(sankoff_bigq_kernel<decltype(P)::value, false, RAGGED>); });
+  return hip_check(fn);
 }
 
-int bigq_run(const char* fn, const WideCall& c) {
-  const int tiles = bigq_tiles(c.L);
+// uniform batches: one item per (tree, 16 sites); ragged ones: the plan's
+// (tree, 64-site) items, per-item partials summed per tree by the ragged
+// partial reduce
+int bigq_run(const char* fn, const SankoffCall& c) {
+  const bool ragged = c.rmeta != nullptr;
+  const int tiles = ragged ? 0 : bigq_tiles(c.L);
   const size_t lds = bigq_lds_bytes(c.n_slots, c.Q);
   if (c.Q > kBigMaxQ) return set_error(TREX_E_UNSUPPORTED, "%s: Q=%d > %d", fn, c.Q, kBigMaxQ);
   if (lds > 160 * 1024) return set_error(TREX_E_UNSUPPORTED, "%s: LDS stack too deep", fn);
   if ((int64_t)c.B * tiles > 0x7FFFFFFF) return set_error(TREX_E_ARG, "%s: grid too large", fn);
+  const int64_t nb = ragged ? c.items : (int64_t)c.B * tiles;
   BigArgs A;
+  fill_common(A, c, ragged ? 0 : c.ni, c.L, tiles, nb);
   A.steps = reinterpret_cast<const int4*>(c.steps);
-  A.leaves = c.leaves;
-  A.cost = c.cost;
-  A.n_int = c.ni;
-  A.nl = c.nl;
-  A.L = c.L;
-  A.tiles = tiles;
-  A.B = c.B;
   A.Q = c.Q;
   A.n_slots = c.n_slots;
-  A.a = c.a;
-  A.bcoef = c.bcoef;
-  A.hard_root = c.hard_root;
-  A.dp = c.dp;
-  A.site_score = c.site_score;
-  A.dts = c.dts;
-  A.marg = c.marg;
-  A.anc = c.anc;
-  const int64_t nb = (int64_t)c.B * tiles;
-  A.part_tree = static_cast<double*>(c.workspace);
-  A.part_dc = A.part_tree + nb;
-  A.rmeta = nullptr;
-  A.ritem = nullptr;
-  A.nitems = 0;
-  if (int e = bigq_launch<false>(fn, A, c, (int64_t)nb, lds)) return e;
-  return partial_reduce(fn, A.part_tree, A.part_dc, c.B, tiles, c.Q, c.phase, c.tree_score,
-                        c.d_cost, c.stream);
-}
-
-// ragged batches: the plan's (tree, 64-site) items, per-item partials summed
-// per tree by the ragged partial reduce
-int bigq_ragged_run(const char* fn, const WideCall& c, const int* rmeta, const int* ritem,
-                    int64_t items) {
-  const size_t lds = bigq_lds_bytes(c.n_slots, c.Q);
-  if (c.Q > kBigMaxQ) return set_error(TREX_E_UNSUPPORTED, "%s: Q=%d > %d", fn, c.Q, kBigMaxQ);
-  if (lds > 160 * 1024) return set_error(TREX_E_UNSUPPORTED, "%s: LDS stack too deep", fn);
-  BigArgs A;
-  A.steps = reinterpret_cast<const int4*>(c.steps);
-  A.leaves = c.leaves;
-  A.cost = c.cost;
-  A.n_int = 0;
-  A.nl = c.nl;
-  A.L = 0;
-  A.tiles = 0;
-  A.B = c.B;
-  A.Q = c.Q;
-  A.n_slots = c.n_slots;
-  A.a = c.a;
-  A.bcoef = c.bcoef;
-  A.hard_root = c.hard_root;
-  A.dp = c.dp;
-  A.site_score = c.site_score;
-  A.dts = c.dts;
-  A.marg = c.marg;
-  A.anc = c.anc;
-  A.part_tree = static_cast<double*>(c.workspace);
-  A.part_dc = A.part_tree + items;
-  A.rmeta = rmeta;
-  A.ritem = ritem;
-  A.nitems = (int)items;
-  if (int e = bigq_launch<true>(fn, A, c, items, lds)) return e;
-  return partial_reduce(fn, A.part_tree, A.part_dc, c.B, 0, c.Q, c.phase, c.tree_score, c.d_cost,
-                        c.stream, rmeta + 5, kRaggedMeta, (int)items);
+  A.rmeta = c.rmeta;
+  A.ritem = c.ritem;
+  A.nitems = (int)c.items;
+  if (int e = !ragged ? bigq_launch<false>(fn, A, c, nb, lds) : bigq_launch<true>(fn, A, c, nb, lds))
+    return e;
+  const RaggedParts rp = ragged_parts(c);
+  return partial_reduce(fn, c, A.part_tree, A.part_dc, tiles, ragged ? &rp : nullptr);
 }
 
 int bigq_backtrack(const int32_t* bt, const float* cost, const float* dp, int B, int L, int ni,
@@ -499,9 +445,7 @@ int bigq_backtrack(const int32_t* bt, const float* cost, const float* dp, int B,
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   hipLaunchKernelGGL(bigq_backtrack_kernel<false>, dim3((unsigned)((int64_t)B * tiles)), dim3(kWave),
                      lds, (hipStream_t)stream, bt, cost, dp, ni, L, Q, tiles, anc, nullptr, 0, 0, 0);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return set_error(TREX_E_HIP, "trex_sankoff_backtrack: %s", hipGetErrorString(e));
-  return TREX_OK;
+  return hip_check("trex_sankoff_backtrack");
 }
 
 int bigq_ragged_backtrack(const int32_t* rmeta, int B, int64_t items, int64_t steps,
@@ -512,10 +456,7 @@ int bigq_ragged_backtrack(const int32_t* rmeta, int B, int64_t items, int64_t st
   hipLaunchKernelGGL(bigq_backtrack_kernel<true>, dim3((unsigned)items), dim3(kWave), lds,
                      (hipStream_t)stream, nullptr, cost, dp, 0, 0, Q, 0, anc, rmeta, B, (int)items,
                      (int)steps);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess)
-    return set_error(TREX_E_HIP, "trex_sankoff_ragged_backtrack: %s", hipGetErrorString(e));
-  return TREX_OK;
+  return hip_check("trex_sankoff_ragged_backtrack");
 }
 
 }  // namespace trex

@@ -10,16 +10,13 @@
 // planner has done that once and the loops switch on a step class and read
 // operands (LDS byte offsets, re-read rows) from a 32-byte record.
 //
-// Scope (run_phase, sankoff.hip, checks it): uniform batch, tau > 0, leaf
+// Scope (route, sankoff.hip, checks it): uniform batch, tau > 0, leaf
 // tile prefetchable (L % 4 == 0, <= 64 leaves), no site scores, marginals or
 // ancestral states; a program exists (no sentinel child, unreached row or
 // two-parent node).  The cost matrix decides on the device as in
 // sankoff_kernel: the factored softmin runs the loops below, the per-row
 // stabilised softmin (range(C) / tau > 40) the generic body.
 #include <hip/hip_runtime.h>
-
-#include <cstdlib>
-#include <cstring>
 
 #include "sankoff_dev.h"
 #include "sankoff_q4_dev.h"
@@ -408,19 +405,10 @@ void sankoff_fused4_kernel(KArgs A, const int* prog) {
 
 int g_fused4_launches = 0;  // tests: which kernel took a call
 
-bool fused4_enabled() {
-  const char* e = std::getenv("TREX_FUSED4");  // read per call (tests run both kernels)
-  return !(e && e[0] == '0');
-}
-
-int fused4_run(const char* fn, const void* kargs, size_t kargs_bytes, const int32_t* prog,
-               size_t lds, void* stream) {
-  KArgs A;
-  if (kargs_bytes != sizeof(A))
-    return set_error(TREX_E_ARG, "%s: kernel argument size mismatch", fn);
-  std::memcpy(&A, kargs, sizeof(A));
+int fused4_run(const char* fn, const SankoffCall& c, const int32_t* prog, size_t lds) {
+  const KArgs A = q4_args(c);
   const int grid = (A.nblocks + 7) / 8 * 8;
-  hipLaunchKernelGGL(sankoff_fused4_kernel, dim3(grid), dim3(kWave), lds, (hipStream_t)stream, A,
+  hipLaunchKernelGGL(sankoff_fused4_kernel, dim3(grid), dim3(kWave), lds, (hipStream_t)c.stream, A,
                      reinterpret_cast<const int*>(prog + TREX_PLAN_HEADER_INTS));
   ++g_fused4_launches;
   return hip_check(fn);

@@ -405,6 +405,27 @@ struct KArgs {
   const int* ritem;     // [nblocks] tree of each work item
 };
 
+// host: the Q <= 4 kernels' arguments of a call.  A uniform batch has one item
+// per (tree, 64 sites) and its partials behind the workspace's counters; a
+// ragged one the plan's items and its partials at the workspace's start.
+inline int q4_tiles(int L) { return (L + kWave - 1) / kWave; }
+inline int64_t q4_counters_bytes(int B) { return ((int64_t)4 * (B + 1) + 255) / 256 * 256; }
+inline KArgs q4_args(const SankoffCall& c) {
+  const bool ragged = c.rmeta != nullptr;
+  const int tiles = ragged ? 0 : q4_tiles(c.L);
+  KArgs A;
+  A.nblocks = ragged ? (int)c.items : c.B * tiles;
+  fill_common(A, c, ragged ? 0 : c.ni, c.L, tiles, A.nblocks,
+              ragged ? 0 : q4_counters_bytes(c.B));
+  A.steps = reinterpret_cast<const int4*>(c.steps);
+  A.n_slots = c.n_slots;
+  A.tree_score = c.tree_score;
+  A.d_cost = c.d_cost;
+  A.rmeta = c.rmeta;
+  A.ritem = c.ritem;
+  return A;
+}
+
 // ragged plan per-tree record (ints): steps offset (in steps), n_int, n_leaves,
 // L, first site (site_score offset), first work item, leaf byte offset (lo, hi),
 // row-site offset of the tree's DP rows (lo, hi; x Q floats), 2 spare

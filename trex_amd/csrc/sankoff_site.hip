@@ -853,58 +853,40 @@ size_t site_lds_bytes(int n_slots, int nl, int ni) {
 }
 
 // host-side eligibility (the cost-dependent mode is decided on the device):
-// soft, 4 < Q <= 20, every tree has a lane program whose slots fit the LDS
-bool site_srow_on() {
-  const char* e = std::getenv("TREX_SITE_SROW");  // "0": the adjoint recomputes s (A/B)
-  return !(e && e[0] == '0');
-}
-
-bool site_eligible(const WideCall& c, int lp_slots) {
+// soft, 4 < Q <= 20, every tree has a lane program whose slots fit the LDS;
+// TREX_SITE=0: the state-parallel kernel (A/B)
+bool site_eligible(const SankoffCall& c, int lp_slots) {
   if (!c.soft || c.Q <= 4 || c.Q > kSQ || lp_slots < 0) return false;
-  const char* e = std::getenv("TREX_SITE");  // "0": the state-parallel kernel (A/B)
-  if (e && e[0] == '0') return false;
+  if (env_switch("TREX_SITE") == 0) return false;
   if ((int64_t)c.ni * c.L * c.Q * 4 > 0x7FFFFFF0LL) return false;
   return site_lds_bytes(lp_slots, c.nl, c.ni) <= kLdsPerCu;
 }
 
-int site_run(const char* fn, const WideCall& c, const int32_t* lanes, int lp_slots,
-             const int* flag, const float* kg) {
+int site_run(const char* fn, const SankoffCall& c, const int32_t* lanes, int lp_slots) {
   const int tiles = site_tiles(c.L);
   const size_t lds = site_lds_bytes(lp_slots, c.nl, c.ni);
   if ((int64_t)c.B * tiles > 0x7FFFFFFF) return set_error(TREX_E_ARG, "%s: grid too large", fn);
   hipStream_t st = (hipStream_t)c.stream;
-  SiteArgs A = site_args<SiteArgs>(c, lanes, lp_slots, flag, kg, tiles);
-  {
-    const char* e = std::getenv("TREX_SITE_CHERRY");  // read per call (tests flip it)
-    A.cherry = !(e && e[0] == '0');
-  }
+  SiteArgs A = site_args<SiteArgs>(c, lanes, lp_slots, tiles);
+  A.cherry = env_switch("TREX_SITE_CHERRY") != 0;
   const bool ks = A.srow != nullptr;
-  if (c.Q == kSQ && !A.cherry) {  // A/B: no cherry tables, no kept s rows
-    if (c.phase == 1)
-      launch_site<1, kSQ, false, false>(A, lds, st);
-    else if (c.phase == 2)
-      launch_site<2, kSQ, false, false>(A, lds, st);
-    else
-      launch_site<3, kSQ, false, false>(A, lds, st);
-  } else if (c.Q == kSQ) {
-    if (c.phase == 1)
-      launch_site<1, kSQ>(A, lds, st);
-    else if (c.phase == 2)
-      launch_site<2, kSQ>(A, lds, st);
-    else if (ks)
-      launch_site<3, kSQ, true>(A, lds, st);
-    else
-      launch_site<3, kSQ>(A, lds, st);
-  } else {
-    if (c.phase == 1)
-      launch_site<1, 0>(A, lds, st);
-    else if (c.phase == 2)
-      launch_site<2, 0>(A, lds, st);
-    else if (ks)
-      launch_site<3, 0, true>(A, lds, st);
-    else
-      launch_site<3, 0>(A, lds, st);
-  }
+  // the kept-s-rows variants exist for the fused phase only
+  auto go = [&](auto qc, auto ch) {
+    constexpr int QC = decltype(qc)::value;
+    constexpr bool CH = decltype(ch)::value;
+    with_phase(c.phase, [&](auto P) {
+      constexpr int PH = decltype(P)::value;
+      if constexpr (PH == 3 && CH)
+        if (ks) return launch_site<3, QC, true>(A, lds, st);
+      launch_site<PH, QC, false, CH>(A, lds, st);
+    });
+  };
+  if (c.Q == kSQ && !A.cherry)  // A/B: no cherry tables, no kept s rows
+    go(std::integral_constant<int, kSQ>(), std::false_type());
+  else if (c.Q == kSQ)
+    go(std::integral_constant<int, kSQ>(), std::true_type());
+  else
+    go(std::integral_constant<int, 0>(), std::true_type());
   return hip_check(fn);
 }
 

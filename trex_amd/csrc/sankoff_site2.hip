@@ -898,37 +898,30 @@ bool site2_on(int lp_slots, int nl, int ni) { return site2_pairs(lp_slots, nl, n
 
 static int g_site2_launches = 0;  // host-side count (tests: the pair kernel did run)
 
-int site2_run(const char* fn, const WideCall& c, const int32_t* lanes, int lp_slots,
-              const int* flag, const float* kg) {
+int site2_run(const char* fn, const SankoffCall& c, const int32_t* lanes, int lp_slots) {
   const int np = site2_pairs(lp_slots, c.nl, c.ni);
   if (np == 0) return set_error(TREX_E_ARG, "%s: the wave-pair kernel does not fit", fn);
   const int tiles = site_tiles(c.L);
   const size_t lds = site2_lds_bytes(np, lp_slots, c.nl, c.ni);
   if ((int64_t)c.B * tiles > 0x7FFFFFFF) return set_error(TREX_E_ARG, "%s: grid too large", fn);
   hipStream_t st = (hipStream_t)c.stream;
-  const Site2Args A = site_args<Site2Args>(c, lanes, lp_slots, flag, kg, tiles);
+  const Site2Args A = site_args<Site2Args>(c, lanes, lp_slots, tiles);
+  const bool ks = A.srow != nullptr;
   auto pick = [&](auto np_c) {
     constexpr int NP = decltype(np_c)::value;
-    const bool ks = A.srow != nullptr;
-    if (c.Q == kSQ) {
-      if (c.phase == 1)
-        launch_site2<1, kSQ, false, NP>(A, lds, st);
-      else if (c.phase == 2)
-        launch_site2<2, kSQ, false, NP>(A, lds, st);
-      else if (ks)
-        launch_site2<3, kSQ, true, NP>(A, lds, st);
-      else
-        launch_site2<3, kSQ, false, NP>(A, lds, st);
-    } else {
-      if (c.phase == 1)
-        launch_site2<1, 0, false, NP>(A, lds, st);
-      else if (c.phase == 2)
-        launch_site2<2, 0, false, NP>(A, lds, st);
-      else if (ks)
-        launch_site2<3, 0, true, NP>(A, lds, st);
-      else
-        launch_site2<3, 0, false, NP>(A, lds, st);
-    }
+    auto go = [&](auto qc) {
+      constexpr int QC = decltype(qc)::value;
+      with_phase(c.phase, [&](auto P) {
+        constexpr int PH = decltype(P)::value;
+        if constexpr (PH == 3)  // the kept-s-rows variants exist for the fused phase only
+          if (ks) return launch_site2<3, QC, true, NP>(A, lds, st);
+        launch_site2<PH, QC, false, NP>(A, lds, st);
+      });
+    };
+    if (c.Q == kSQ)
+      go(std::integral_constant<int, kSQ>());
+    else
+      go(std::integral_constant<int, 0>());
   };
   if (np == 8)
     pick(std::integral_constant<int, 8>());

@@ -551,12 +551,7 @@ void launch_staged(int phase, int grid, size_t lds, hipStream_t st, const SArgs&
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(kSW * kWave), lds, st, A);
   };
-  if (phase == 1)
-    go(sankoff_staged_kernel<G, SOFT, 1>);
-  else if (phase == 2)
-    go(sankoff_staged_kernel<G, SOFT, 2>);
-  else
-    go(sankoff_staged_kernel<G, SOFT, 3>);
+  with_phase(phase, [&](auto P) { go(sankoff_staged_kernel<G, SOFT, decltype(P)::value>); });
 }
 
 template <int G>
@@ -600,7 +595,7 @@ size_t staged_lds_bytes(int ni, int nl, int Q, int phase) {
   }
 }
 
-int staged_run(const char* fn, const WideCall& c, const int32_t* staged) {
+int staged_run(const char* fn, const SankoffCall& c, const int32_t* staged) {
   if (c.Q > 32) return set_error(TREX_E_UNSUPPORTED, "%s: staged kernel needs Q <= 32", fn);
   const int tiles = wide_tiles(c.L, c.Q);
   const size_t lds = staged_lds_bytes(c.ni, c.nl, c.Q, c.phase);
@@ -608,28 +603,12 @@ int staged_run(const char* fn, const WideCall& c, const int32_t* staged) {
   if ((int64_t)c.B * tiles > 0x7FFFFFFF) return set_error(TREX_E_ARG, "%s: grid too large", fn);
   if ((int64_t)c.ni * c.L * c.Q * 4 > 0x7FFFFFF0LL)
     return set_error(TREX_E_UNSUPPORTED, "%s: one tree's DP table exceeds 2 GiB", fn);
+  const int64_t nb = (int64_t)c.B * tiles;
   SArgs A;
+  fill_common(A, c, c.ni, c.L, tiles, nb);
   A.staged = staged;
   A.stride = staged_tree_ints(c.ni);
-  A.leaves = c.leaves;
-  A.cost = c.cost;
-  A.n_int = c.ni;
-  A.nl = c.nl;
-  A.L = c.L;
-  A.tiles = tiles;
-  A.B = c.B;
   A.Q = c.Q;
-  A.a = c.a;
-  A.bcoef = c.bcoef;
-  A.hard_root = c.hard_root;
-  A.dp = c.dp;
-  A.site_score = c.site_score;
-  A.dts = c.dts;
-  A.marg = c.marg;
-  A.anc = c.anc;
-  const int64_t nb = (int64_t)c.B * tiles;
-  A.part_tree = static_cast<double*>(c.workspace);
-  A.part_dc = A.part_tree + nb;
   // the counter sits in the workspace's tail slack (wide_workspace_bytes)
   A.counter = reinterpret_cast<unsigned*>(A.part_dc + nb * c.Q * c.Q);
   A.tree_score = c.tree_score;
@@ -650,11 +629,9 @@ int staged_run(const char* fn, const WideCall& c, const int32_t* staged) {
     case 20: launch_staged_g<20>(c.phase, c.soft, grid, lds, st, A); break;
     default: launch_staged_g<32>(c.phase, c.soft, grid, lds, st, A); break;
   }
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return set_error(TREX_E_HIP, "%s: %s", fn, hipGetErrorString(e));
+  if (int e = hip_check(fn)) return e;
   if (A.tail) return TREX_OK;  // partials reduced by the kernel's last workgroup
-  return partial_reduce(fn, A.part_tree, A.part_dc, c.B, tiles, c.Q, c.phase, c.tree_score,
-                        c.d_cost, c.stream, nullptr, 0, 0, 1, c.mx_flag, c.mx_tiles);
+  return partial_reduce(fn, c, A.part_tree, A.part_dc, tiles);
 }
 
 }  // namespace trex

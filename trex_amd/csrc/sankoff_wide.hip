@@ -22,7 +22,6 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstdlib>
 
 #include "sankoff_dev.h"
 #include "trex_common.h"
@@ -718,12 +717,10 @@ __global__ __launch_bounds__(kWave) void wide_backtrack4_kernel(const int* __res
 
 template <int G, bool SOFT, bool RAGGED>
 void launch_wide(int phase, int grid, size_t lds, hipStream_t st, const WArgs& A) {
-  if (phase == 1)
-    hipLaunchKernelGGL((sankoff_wide_kernel<G, SOFT, 1, RAGGED>), dim3(grid), dim3(kWave), lds, st, A);
-  else if (phase == 2)
-    hipLaunchKernelGGL((sankoff_wide_kernel<G, SOFT, 2, RAGGED>), dim3(grid), dim3(kWave), lds, st, A);
-  else
-    hipLaunchKernelGGL((sankoff_wide_kernel<G, SOFT, 3, RAGGED>), dim3(grid), dim3(kWave), lds, st, A);
+  with_phase(phase, [&](auto P) {
+    hipLaunchKernelGGL((sankoff_wide_kernel<G, SOFT, decltype(P)::value, RAGGED>), dim3(grid),
+                       dim3(kWave), lds, st, A);
+  });
 }
 
 template <int G, bool RAGGED = false>
@@ -763,10 +760,10 @@ int64_t wide_workspace_bytes(int B, int L, int Q) {
   // tail: staged-kernel counter (128 B) | cherry tables (36 KB) and K and
   // K^T (3.25 KB) for the lane-per-site kernel (sankoff_site.hip) | mode
   // flag (128 B)
-  return nb * 8 * (1 + (int64_t)Q * Q) + 3584 + kSiteTabBytes;
+  return nb * 8 * (1 + (int64_t)Q * Q) + 128 + kSiteTabBytes + kWideTailKg;
 }
 
-int wide_run(const char* fn, const WideCall& c, bool reduce) {
+int wide_run(const char* fn, const SankoffCall& c, bool reduce) {
   const int tiles = wide_tiles(c.L, c.Q);
   size_t lds = wide_lds_bytes(c.n_slots, c.nl, c.ni, c.Q);
   // a gated launch may build the site kernel's cherry tables in its LDS
@@ -775,37 +772,20 @@ int wide_run(const char* fn, const WideCall& c, bool reduce) {
   if ((int64_t)c.B * tiles > 0x7FFFFFFF) return set_error(TREX_E_ARG, "%s: grid too large", fn);
   if ((int64_t)c.ni * c.L * c.Q * 4 > 0x7FFFFFF0LL)
     return set_error(TREX_E_UNSUPPORTED, "%s: one tree's DP table exceeds 2 GiB", fn);
+  const int grid = c.B * tiles;
   WArgs A;
+  fill_common(A, c, c.ni, c.L, tiles, grid);
   A.steps = c.steps;
-  A.leaves = c.leaves;
-  A.cost = c.cost;
-  A.n_int = c.ni;
-  A.nl = c.nl;
-  A.L = c.L;
-  A.tiles = tiles;
-  A.B = c.B;
   A.n_slots = c.n_slots;
   A.Q = c.Q;
-  A.a = c.a;
-  A.bcoef = c.bcoef;
-  A.hard_root = c.hard_root;
-  A.dp = c.dp;
-  A.site_score = c.site_score;
-  A.dts = c.dts;
-  A.marg = c.marg;
-  A.anc = c.anc;
   A.rmeta = nullptr;
   A.ritem = nullptr;
   A.wpi = 0;
   A.skip = c.mx_flag;
   A.site_flag = c.site_flag;
   A.site_kg = c.site_kg;
-  const int64_t nb = (int64_t)c.B * tiles;
-  A.nitems = (int)nb;
-  A.part_tree = static_cast<double*>(c.workspace);
-  A.part_dc = A.part_tree + nb;
+  A.nitems = grid;
   hipStream_t st = (hipStream_t)c.stream;
-  const int grid = (int)nb;
   switch (wide_group(c.Q)) {
     case 4: launch_wide_g<4>(c.phase, c.soft, grid, lds, st, A); break;
     case 8: launch_wide_g<8>(c.phase, c.soft, grid, lds, st, A); break;
@@ -814,11 +794,9 @@ int wide_run(const char* fn, const WideCall& c, bool reduce) {
     case 32: launch_wide_g<32>(c.phase, c.soft, grid, lds, st, A); break;
     default: launch_wide_g<64>(c.phase, c.soft, grid, lds, st, A); break;
   }
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return set_error(TREX_E_HIP, "%s: %s", fn, hipGetErrorString(e));
+  if (int e = hip_check(fn)) return e;
   if (!reduce) return TREX_OK;
-  return partial_reduce(fn, A.part_tree, A.part_dc, c.B, tiles, c.Q, c.phase, c.tree_score,
-                        c.d_cost, c.stream, nullptr, 0, 0, 1, c.mx_flag, c.mx_tiles);
+  return partial_reduce(fn, c, A.part_tree, A.part_dc, tiles);
 }
 
 // waves per 64-site ragged item: ceil(64 / sites per wave)
@@ -831,39 +809,22 @@ int64_t wide_ragged_workspace_bytes(int64_t items, int Q) {
   return items * wide_ragged_wpi(Q) * 8 * (1 + (int64_t)Q * Q) + 256;
 }
 
-int wide_ragged_run(const char* fn, const WideCall& c, const int* rmeta, const int* ritem,
-                    int64_t items) {
+int wide_ragged_run(const char* fn, const SankoffCall& c) {
   const int wpi = wide_ragged_wpi(c.Q);
   const size_t lds = wide_lds_bytes(c.n_slots, c.nl, c.nl - 1, c.Q);
   if (lds > 65536) return set_error(TREX_E_UNSUPPORTED, "%s: LDS stack too deep", fn);
-  if (items * wpi > 0x7FFFFFFF) return set_error(TREX_E_ARG, "%s: grid too large", fn);
+  if (c.items * wpi > 0x7FFFFFFF) return set_error(TREX_E_ARG, "%s: grid too large", fn);
+  const int grid = (int)(c.items * wpi);
   WArgs A;
+  fill_common(A, c, 0, 0, 0, grid);  // c.nl: max leaves (LDS leaf tile, stabiliser rows)
   A.steps = c.steps;
-  A.leaves = c.leaves;
-  A.cost = c.cost;
-  A.n_int = 0;
-  A.nl = c.nl;  // max leaves (LDS leaf tile, stabiliser rows)
-  A.L = 0;
-  A.tiles = 0;
-  A.B = c.B;
   A.n_slots = c.n_slots;
   A.Q = c.Q;
-  A.a = c.a;
-  A.bcoef = c.bcoef;
-  A.hard_root = c.hard_root;
-  A.dp = c.dp;
-  A.site_score = c.site_score;
-  A.dts = c.dts;
-  A.marg = c.marg;
-  A.anc = c.anc;
-  A.rmeta = rmeta;
-  A.ritem = ritem;
+  A.rmeta = c.rmeta;
+  A.ritem = c.ritem;
   A.wpi = wpi;
   A.skip = nullptr;  // ragged batches never run the matrix-core kernel
-  const int grid = (int)(items * wpi);
   A.nitems = grid;
-  A.part_tree = static_cast<double*>(c.workspace);
-  A.part_dc = A.part_tree + grid;
   hipStream_t st = (hipStream_t)c.stream;
   switch (wide_group(c.Q)) {
     case 8: launch_wide_g<8, true>(c.phase, c.soft, grid, lds, st, A); break;
@@ -872,39 +833,35 @@ int wide_ragged_run(const char* fn, const WideCall& c, const int* rmeta, const i
     case 32: launch_wide_g<32, true>(c.phase, c.soft, grid, lds, st, A); break;
     default: launch_wide_g<64, true>(c.phase, c.soft, grid, lds, st, A); break;
   }
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return set_error(TREX_E_HIP, "%s: %s", fn, hipGetErrorString(e));
-  return partial_reduce(fn, A.part_tree, A.part_dc, c.B, 0, c.Q, c.phase, c.tree_score, c.d_cost,
-                        c.stream, rmeta + 5, kRaggedMeta, (int)items, wpi);
+  if (int e = hip_check(fn)) return e;
+  const RaggedParts rp = ragged_parts(c, wpi);
+  return partial_reduce(fn, c, A.part_tree, A.part_dc, 0, &rp);
 }
 
-int partial_reduce(const char* fn, const double* part_tree, const double* part_dc, int B,
-                   int tiles, int Q, int phase, float* tree_score, float* d_cost, void* stream,
-                   const int* first, int first_stride, int items, int first_scale,
-                   const int* mx_flag, int mx_tiles) {
-  const bool do_tree = (phase & 1) != 0;
-  const bool do_dc = (phase & 2) != 0;
+int partial_reduce(const char* fn, const SankoffCall& c, const double* part_tree,
+                   const double* part_dc, int tiles, const RaggedParts* ragged) {
+  const bool do_tree = (c.phase & 1) != 0;
+  const bool do_dc = (c.phase & 2) != 0;
+  const int B = c.B, QQ = c.Q * c.Q;
+  hipStream_t st = (hipStream_t)c.stream;
   const int64_t nb = (int64_t)B * tiles;
-  if (!first && !mx_flag && do_dc && nb > TREX_REDUCE2_MIN) {
+  if (!ragged && !c.mx_flag && do_dc && nb > TREX_REDUCE2_MIN) {
     const int P = (int)((nb + kChunk - 1) / kChunk);
-    const int ndc = Q * Q * P;
+    const int ndc = QQ * P;
     const int tblocks = do_tree ? (B + kStage1Threads / kWave - 1) / (kStage1Threads / kWave) : 0;
-    hipLaunchKernelGGL(reduce_stage1_kernel, dim3(ndc + tblocks), dim3(kStage1Threads), 0,
-                       (hipStream_t)stream, part_tree, const_cast<double*>(part_dc), B, tiles, ndc,
-                       P, do_tree ? 1 : 0, tree_score);
-    hipLaunchKernelGGL(reduce_stage2_kernel, dim3(Q * Q), dim3(kWave), 0, (hipStream_t)stream,
-                       part_dc, B, tiles, P, d_cost);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(TREX_E_HIP, "%s: %s", fn, hipGetErrorString(e));
-    return TREX_OK;
+    hipLaunchKernelGGL(reduce_stage1_kernel, dim3(ndc + tblocks), dim3(kStage1Threads), 0, st,
+                       part_tree, const_cast<double*>(part_dc), B, tiles, ndc, P, do_tree ? 1 : 0,
+                       c.tree_score);
+    hipLaunchKernelGGL(reduce_stage2_kernel, dim3(QQ), dim3(kWave), 0, st, part_dc, B, tiles, P,
+                       c.d_cost);
+    return hip_check(fn);
   }
-  const int rgrid = (do_tree ? B : 0) + (do_dc ? Q * Q : 0);
-  hipLaunchKernelGGL(wide_reduce_kernel, dim3(rgrid), dim3(kReduceThreads), 0, (hipStream_t)stream,
-                     part_tree, part_dc, B, tiles, Q * Q, do_tree ? 1 : 0, tree_score, d_cost,
-                     first, first_stride, items, first_scale, mx_flag, mx_tiles);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return set_error(TREX_E_HIP, "%s: %s", fn, hipGetErrorString(e));
-  return TREX_OK;
+  const RaggedParts r = ragged ? *ragged : RaggedParts{nullptr, 0, 0, 1};
+  const int rgrid = (do_tree ? B : 0) + (do_dc ? QQ : 0);
+  hipLaunchKernelGGL(wide_reduce_kernel, dim3(rgrid), dim3(kReduceThreads), 0, st, part_tree,
+                     part_dc, B, tiles, QQ, do_tree ? 1 : 0, c.tree_score, c.d_cost, r.first,
+                     r.stride, r.items, r.scale, c.mx_flag, c.mx_tiles);
+  return hip_check(fn);
 }
 
 int wide_ragged_backtrack(const int32_t* rmeta, int B, int64_t items, int64_t steps,
@@ -919,10 +876,7 @@ int wide_ragged_backtrack(const int32_t* rmeta, int B, int64_t items, int64_t st
     hipLaunchKernelGGL((wide_backtrack_kernel<64, true>), dim3((int)items), dim3(kWave), lds,
                        (hipStream_t)stream, nullptr, cost, dp, 0, 0, Q, 0, anc, rmeta, B,
                        (int)items, (int)steps);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess)
-    return set_error(TREX_E_HIP, "trex_sankoff_ragged_backtrack: %s", hipGetErrorString(e));
-  return TREX_OK;
+  return hip_check("trex_sankoff_ragged_backtrack");
 }
 
 int wide_backtrack(const int32_t* bt, const float* cost, const float* dp, int B, int L, int ni,
@@ -930,9 +884,8 @@ int wide_backtrack(const int32_t* bt, const float* cost, const float* dp, int B,
   // TREX_BT4=0 forces the one-lane-per-site kernel (live for codons, ragged
   // batches and trees too deep for the split kernel's LDS; the tests run it
   // on Q <= 32 too).  8 lanes per site for Q > 4; Q <= 4 (one state per lane): 4
-  const char* e4 = std::getenv("TREX_BT4");
   const int lps = Q <= 4 ? 4 : 8;
-  if (Q <= 32 && !(e4 && e4[0] == '0') && (int64_t)ni * L * Q * 4 <= 0x7FFFFFF0LL &&
+  if (Q <= 32 && env_switch("TREX_BT4") != 0 && (int64_t)ni * L * Q * 4 <= 0x7FFFFFF0LL &&
       32 * 32 * 4 + (size_t)ni * (kWave / lps) <= 65536) {
     const int spw = kWave / lps;
     const int tiles4 = (L + spw - 1) / spw;
@@ -943,10 +896,7 @@ int wide_backtrack(const int32_t* bt, const float* cost, const float* dp, int B,
     else
       hipLaunchKernelGGL(wide_backtrack4_kernel<4>, dim3(B * tiles4), dim3(kWave), lds4,
                          (hipStream_t)stream, bt, cost, dp, ni, L, Q, tiles4, anc);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess)
-      return set_error(TREX_E_HIP, "trex_sankoff_backtrack: %s", hipGetErrorString(e));
-    return TREX_OK;
+    return hip_check("trex_sankoff_backtrack");
   }
   const int tiles = (L + kWave - 1) / kWave;
   const int mq = Q <= 32 ? 32 : 64;
@@ -964,10 +914,7 @@ int wide_backtrack(const int32_t* bt, const float* cost, const float* dp, int B,
     go(wide_backtrack_kernel<32, false>);
   else
     go(wide_backtrack_kernel<64, false>);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess)
-    return set_error(TREX_E_HIP, "trex_sankoff_backtrack: %s", hipGetErrorString(e));
-  return TREX_OK;
+  return hip_check("trex_sankoff_backtrack");
 }
 
 }  // namespace trex

@@ -1,14 +1,13 @@
 // What the two lane-per-site translation units share (sankoff_site.hip: one
 // wave per 64 sites; sankoff_site2.hip: a wave pair): the kernel arguments
-// and their host fill, the LDS sizes, the bf16 split, the barrier, the stamp
-// macro and two prologue pieces.  The row I/O, mat-vec, adjoint and dC code
-// differs between the mappings and stays in each kernel.
+// and their host fill (over fill_common), the LDS sizes, the bf16 split, the
+// barrier, the stamp macro and two prologue pieces.  The row I/O, mat-vec,
+// adjoint and dC code differs between the mappings and stays in each kernel.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdlib>
 
 #include "sankoff_dev.h"
 #include "trex_common.h"
@@ -68,36 +67,20 @@ struct SiteArgs {
   int n_slots;
 };
 
-// the arguments of a call but the one-wave kernel's cherry (Args: SiteArgs,
-// or the pair kernel's Site2Args)
+// the arguments of a call, behind a gated wide_run (c.site_flag / c.site_kg),
+// but the one-wave kernel's cherry (Args: SiteArgs, or the pair kernel's
+// Site2Args)
 template <class Args>
-Args site_args(const WideCall& c, const int32_t* lanes, int lp_slots, const int* flag,
-               const float* kg, int tiles) {
+Args site_args(const SankoffCall& c, const int32_t* lanes, int lp_slots, int tiles) {
   Args A;
+  fill_common(A, c, c.ni, c.L, tiles, (int64_t)c.B * tiles);
   A.lanes = lanes;
   A.stride = lp_tree_ints(c.ni);
-  A.leaves = c.leaves;
-  A.cost = c.cost;
-  A.n_int = c.ni;
-  A.nl = c.nl;
-  A.L = c.L;
-  A.tiles = tiles;
-  A.B = c.B;
   A.Q = c.Q;
-  A.a = c.a;
-  A.bcoef = c.bcoef;
-  A.hard_root = c.hard_root;
-  A.dp = c.dp;
-  A.site_score = c.site_score;
-  A.dts = c.dts;
-  A.marg = c.marg;
-  A.anc = c.anc;
-  A.part_tree = static_cast<double*>(c.workspace);
-  A.part_dc = A.part_tree + (int64_t)c.B * tiles;
-  A.kg = kg;
-  A.ptab = kg - kSiteTabBytes / 4;
+  A.kg = c.site_kg;
+  A.ptab = c.site_kg - kSiteTabBytes / 4;
   A.srow = c.phase == 3 ? c.site_srow : nullptr;
-  A.flag = flag;
+  A.flag = c.site_flag;
   A.n_slots = lp_slots;
   return A;
 }

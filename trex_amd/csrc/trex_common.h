@@ -5,7 +5,9 @@
 #include <cstddef>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
+#include <type_traits>
 
 #include "../../include/trex_hip.h"
 
@@ -93,13 +95,6 @@ constexpr int32_t kF4Put = 512;                  // the forward writes the node'
 constexpr int kF4Cherry = 0, kF4CherryDeferred = 1, kF4LeafInt = 2, kF4IntInt = 3;
 constexpr int kF4FwdClassShift = 16;
 constexpr int32_t kF4NoRow = -1;
-// launches the fused Q = 4 kernel on a call run_phase (sankoff.hip) found in
-// scope; kargs: its KArgs (the kernels' argument struct is private to each
-// translation unit, hence the bytes), prog: the device copy of the program
-bool fused4_enabled();  // TREX_FUSED4 != "0" (read per call)
-int fused4_run(const char* fn, const void* kargs, size_t kargs_bytes, const int32_t* prog,
-               size_t lds, void* stream);
-
 // backtrack entry kinds (bits 16-19 of word 0)
 constexpr int kBtRoot = 0;
 constexpr int kBtReal = 1;
@@ -133,8 +128,31 @@ inline bool pos_finite_f32(float x) {
   return finite_f32(x) && !(u >> 31) && (u & 0x7fffffffu) != 0;
 }
 
-// ---- Q > 4: state-parallel kernels on a site-major DP table (sankoff_wide.hip)
-struct WideCall {
+// 1 / 0 from the first character of an on / off knob, -1 when it is unset or
+// anything else.  Read per call: the tests flip the knobs inside one process.
+// "TREX_X=0 / 1 forces" reads as >= 0, "off when 0" as != 0.
+inline int env_switch(const char* name) {
+  const char* e = std::getenv(name);
+  return e && (e[0] == '0' || e[0] == '1') ? e[0] - '0' : -1;
+}
+
+// a run-time phase (1 fwd, 2 adjoint, 3 fused) as a compile-time one:
+// f(std::integral_constant<int, PHASE>())
+template <class F>
+void with_phase(int phase, F&& f) {
+  if (phase == 1)
+    f(std::integral_constant<int, 1>());
+  else if (phase == 2)
+    f(std::integral_constant<int, 2>());
+  else
+    f(std::integral_constant<int, 3>());
+}
+
+// ---- one Sankoff call, uniform or ragged, at any Q: the entry point's
+// arguments as every kernel family's host code takes them (sankoff_call,
+// sankoff.hip).  A ragged call has L = 0, the largest tree's nl / ni, and the
+// plan's records in rmeta / ritem / items.
+struct SankoffCall {
   int phase;  // 1 fwd, 2 adjoint, 3 fused
   bool soft;
   const int* steps;
@@ -152,6 +170,11 @@ struct WideCall {
   float* d_cost;
   void* workspace;
   void* stream;
+  // ragged batches (null / 0 for uniform ones): per-tree records, the
+  // work-item -> tree table, the number of 64-site items
+  const int* rmeta = nullptr;
+  const int* ritem = nullptr;
+  int64_t items = 0;
   // set when the lane-per-site kernel (sankoff_site.hip) ran first: the device
   // word it wrote (1: it handled the launch -- the state-parallel kernels
   // exit at once, the reduce sums its mx_tiles partials per tree)
@@ -167,60 +190,97 @@ struct WideCall {
   // the wide workspace, DP-table layout; null: recomputed)
   float* site_srow = nullptr;
 };
+
+// The fields every kernel argument struct (KArgs, WArgs, SArgs, SiteArgs,
+// Site2Args, BigArgs) shares, from a call: a uniform batch of B trees of
+// n_int rows, L sites and tiles items each, or (n_int = L = tiles = 0) a
+// ragged one.  The partials sit part_offset bytes into the workspace: nitems
+// per-item scores, then the [Q*Q][nitems] dC partials.  The launcher sets
+// what is its own.
+template <class Args>
+void fill_common(Args& A, const SankoffCall& c, int n_int, int L, int tiles, int64_t nitems,
+                 int64_t part_offset = 0) {
+  A.leaves = c.leaves;
+  A.cost = c.cost;
+  A.n_int = n_int;
+  A.nl = c.nl;
+  A.L = L;
+  A.tiles = tiles;
+  A.B = c.B;
+  A.a = c.a;
+  A.bcoef = c.bcoef;
+  A.hard_root = c.hard_root;
+  A.dp = c.dp;
+  A.site_score = c.site_score;
+  A.dts = c.dts;
+  A.marg = c.marg;
+  A.anc = c.anc;
+  A.part_tree = reinterpret_cast<double*>(static_cast<char*>(c.workspace) + part_offset);
+  A.part_dc = A.part_tree + nitems;
+}
+
+// the fused Q = 4 kernel (sankoff_fused4.hip) on a call run_phase found in
+// scope; prog: the device copy of the program
+int fused4_run(const char* fn, const SankoffCall& c, const int32_t* prog, size_t lds);
+
+// ---- Q > 4: state-parallel kernels on a site-major DP table (sankoff_wide.hip)
 constexpr int kWideMaxQ = 64;
 // 64 < Q <= 128: the large-alphabet kernel (sankoff_bigq.hip; int8 leaf codes
 // and ancestral states bound Q by 128)
 constexpr int kBigMaxQ = 128;
 int bigq_tiles(int L);
 int64_t bigq_workspace_bytes(int B, int L, int Q);
-int bigq_run(const char* fn, const WideCall& c);
+int bigq_run(const char* fn, const SankoffCall& c);  // uniform or ragged
 int bigq_backtrack(const int32_t* bt, const float* cost, const float* dp, int B, int L, int ni,
                    int Q, int8_t* anc, void* stream);
-int bigq_ragged_run(const char* fn, const WideCall& c, const int* rmeta, const int* ritem,
-                    int64_t items);
 int bigq_ragged_backtrack(const int32_t* rmeta, int B, int64_t items, int64_t steps,
                           const float* cost, const float* dp, int Q, int8_t* anc, void* stream);
-constexpr int kRaggedMeta = 12;  // ints per tree record of a ragged plan (plan.cpp)  // leaf codes and ancestral states are int8
+constexpr int kRaggedMeta = 12;  // ints per tree record of a ragged plan (plan.cpp)
 int wide_group(int Q);
 int wide_tiles(int L, int Q);
 size_t wide_lds_bytes(int n_slots, int nl, int ni, int Q);
+// per-item partials, then a tail (from its end): the site gate's flag (128 B),
+// below it K and K^T of the lane-per-site kernel (3.25 KB), its cherry tables
+// and the staged kernel's counter
 int64_t wide_workspace_bytes(int B, int L, int Q);
-int wide_run(const char* fn, const WideCall& c, bool reduce = true);
+constexpr int kWideTailFlag = 128;  // the flag sits this far below the end
+constexpr int kWideTailKg = 3456;   // and K, K^T this far
+int wide_run(const char* fn, const SankoffCall& c, bool reduce = true);
 // staged multi-wave kernel (sankoff_staged.hip); staged = the plan's staged
 // regions (after the backtrack entries)
 size_t staged_lds_bytes(int ni, int nl, int Q, int phase);
-int staged_run(const char* fn, const WideCall& c, const int32_t* staged);
-// fixed-order sum of per-item partials -> tree_score [B] (phase & 1), d_cost
-// [Q*Q] (phase & 2); part_dc is [Q*Q][B*tiles]
-// (ragged batches: first[b * first_stride] is tree b's first item, items the
-// total; tiles is then unused)
-// (first_scale: partials per item, the wide kernel's waves per ragged item)
-// (mx_flag / mx_tiles: when *mx_flag is set on the device, the partials are
-// the lane-per-site kernel's, mx_tiles per tree)
-int partial_reduce(const char* fn, const double* part_tree, const double* part_dc, int B,
-                   int tiles, int Q, int phase, float* tree_score, float* d_cost, void* stream,
-                   const int* first = nullptr, int first_stride = 0, int items = 0,
-                   int first_scale = 1, const int* mx_flag = nullptr, int mx_tiles = 0);
-// ragged batches with Q > 4 on the wide kernel (rmeta / ritem: the plan's
-// records and item table; c.nl = max leaves, c.L unused)
+int staged_run(const char* fn, const SankoffCall& c, const int32_t* staged);
+// a ragged batch's partials: first[b * stride] is tree b's first item, items
+// the total, scale the partials per item (the wide kernel's waves per item)
+struct RaggedParts {
+  const int* first;
+  int stride, items, scale;
+};
+inline RaggedParts ragged_parts(const SankoffCall& c, int scale = 1) {
+  return {c.rmeta + 5, kRaggedMeta, (int)c.items, scale};
+}
+// fixed-order sum of per-item partials -> c.tree_score [B] (phase & 1),
+// c.d_cost [Q*Q] (phase & 2); part_dc is [Q*Q][B*tiles] (ragged: tiles is
+// unused).  When *c.mx_flag is set on the device, the partials are the
+// lane-per-site kernel's, c.mx_tiles per tree.
+int partial_reduce(const char* fn, const SankoffCall& c, const double* part_tree,
+                   const double* part_dc, int tiles, const RaggedParts* ragged = nullptr);
+// ragged batches with Q > 4 on the wide kernel (c.nl = max leaves)
 int64_t wide_ragged_workspace_bytes(int64_t items, int Q);
-int wide_ragged_run(const char* fn, const WideCall& c, const int* rmeta, const int* ritem,
-                    int64_t items);
+int wide_ragged_run(const char* fn, const SankoffCall& c);
 // lane-per-site kernel for the factored softmin, 4 < Q <= 20 (sankoff_site.hip)
-bool site_eligible(const WideCall& c, int lp_slots);
+bool site_eligible(const SankoffCall& c, int lp_slots);
 constexpr int kSiteMaxQ = 20;  // the lane-per-site kernel's largest Q (kSiteSQ, wide_dev.h)
-bool site_srow_on();  // TREX_SITE_SROW != "0" (read per call)
 inline int64_t site_srow_offset(int B, int L, int Q) {
   return (wide_workspace_bytes(B, L, Q) + 255) / 256 * 256;
 }
 int site_tiles(int L);
-int site_run(const char* fn, const WideCall& c, const int32_t* lanes, int lp_slots,
-             const int* flag, const float* kg);
+// behind a gated wide_run: c.site_flag / c.site_kg are what that wrote
+int site_run(const char* fn, const SankoffCall& c, const int32_t* lanes, int lp_slots);
 // the same with each site's states split over a wave pair (sankoff_site2.hip;
 // TREX_SITE2=1 / 8 / 6 / 4, read per call: the pair count, when its LDS fits)
 bool site2_on(int lp_slots, int nl, int ni);
-int site2_run(const char* fn, const WideCall& c, const int32_t* lanes, int lp_slots,
-              const int* flag, const float* kg);
+int site2_run(const char* fn, const SankoffCall& c, const int32_t* lanes, int lp_slots);
 int wide_backtrack(const int32_t* bt, const float* cost, const float* dp, int B, int L, int ni,
                    int Q, int8_t* anc, void* stream);
 int wide_ragged_backtrack(const int32_t* rmeta, int B, int64_t items, int64_t steps,
