@@ -651,6 +651,39 @@ int trex_sankoff_attach(const int32_t* attach_plan, const int8_t* leaves, const 
                         float* attach_score, void* workspace, int64_t workspace_bytes,
                         void* stream);
 
+/* ------------------------------------------------------------------------
+ * Site weights (pattern counts of a compressed alignment, the parsimony
+ * ratchet's reweighting, bootstrap replicates): weights fp32 [B][L], one row
+ * per tree, finite; scores carry the kernels' relative bar only when the
+ * weights are >= 0 (mixed signs cancel).  A weight multiplies its site's score
+ * in fp64 where the sites are summed and nowhere else: the dp and outside
+ * tables are per site and stay unweighted, and so do the forward and adjoint
+ * kernels.  x * 1.0 is exact in fp64, so all-ones weights give the bits of the
+ * unweighted call.  Weight values are not checked.  Added without a version
+ * bump (trex_version() stays 10).
+ *
+ * trex_site_weighted_sum: tree_score[b] = sum_l weights[b][l] *
+ *   site_score[b][l] (site_score [B][L] as trex_sankoff_fwd writes it):
+ *   products and sum in fp64 in a fixed order, one rounding to fp32, no
+ *   atomics; repeated calls are bitwise equal.  No workspace.
+ * trex_sankoff_nni_w / trex_sankoff_attach_w: trex_sankoff_nni /
+ *   trex_sankoff_attach with `weights` directly after the last input table
+ *   (outside; sub_rows) and before the output.  weights == NULL is the
+ *   unweighted call (trex_sankoff_nni / _attach forward here with NULL).
+ *   Workspace sizes, shape limits and error codes are unchanged.
+ * ---------------------------------------------------------------------- */
+int trex_site_weighted_sum(const float* site_score, const float* weights, int B, int L,
+                           float* tree_score, void* stream);
+int trex_sankoff_nni_w(const int32_t* nni_plan, const int8_t* leaves, const float* cost, int B,
+                       int L, int n_all, int Q, float tau, const float* dp, const float* outside,
+                       const float* weights, float* nni_score, void* workspace,
+                       int64_t workspace_bytes, void* stream);
+int trex_sankoff_attach_w(const int32_t* attach_plan, const int8_t* leaves, const float* cost,
+                          int B, int L, int n_all, int Q, float tau, const float* dp,
+                          const float* outside, const int8_t* sub_codes, const float* sub_rows,
+                          const float* weights, float* attach_score, void* workspace,
+                          int64_t workspace_bytes, void* stream);
+
 /* ========================================================================
  * Synthetic data on the device: trex's
  * generate_groundtruth (src/trex/ground_truth.py:112-197, mutate :20-52) and

@@ -2,7 +2,7 @@
 against what they replace, one forward per candidate edge.
 
     python tools/time_attach.py [--trees 1024] [--taxa 32] [--sites 5000] [--states 4]
-                                [--window 0.5] [--out FILE]
+                                [--window 0.5] [--weights] [--out FILE]
 
 Timed as tools/time_nni.py does (device events around windows of >= --window
 seconds after the clocks have settled).  Per tau (0 and 0.5) one JSON line:
@@ -11,7 +11,9 @@ forward of the (taxa + 1)-taxon trees (every candidate scored as a tree of its
 own, in the same run), the bytes each pass moves by the shapes (no cache reuse
 assumed) and the bytes/s that gives.  As information only: the wall time of
 one stepwise_addition with --trees addition sequences of --taxa taxa, which
-includes the per-step plan rebuilds on the host.
+includes the per-step plan rebuilds on the host.  --weights also times
+attach_scores with uniform(0.25, 2) site weights next to the unweighted call:
+attach_weighted_ms and weighted_over_unweighted.
 """
 import argparse
 import json
@@ -51,6 +53,8 @@ def main():
     ap.add_argument("--sites", type=int, default=5000)
     ap.add_argument("--states", type=int, default=4)
     ap.add_argument("--window", type=float, default=0.5)
+    ap.add_argument("--weights", action="store_true",
+                    help="also time the weighted call (trex_sankoff_attach_w)")
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
@@ -60,6 +64,7 @@ def main():
     g = torch.Generator(device=dev)
     g.manual_seed(6)
     new = torch.randint(0, Q, (B, L), generator=g, device=dev, dtype=torch.int8)
+    w = torch.rand((B, L), generator=g, device=dev) * 1.75 + 0.25 if a.weights else None
     # the grown trees a forward per edge would score: n + 1 taxa
     big = SankoffEngine(TreePlan(random_topologies(B, n + 1, seed=4)), L, Q, dev)
     big_leaves = torch.cat([leaves, new[:, None]], dim=1).contiguous()
@@ -98,6 +103,13 @@ def main():
             "outside_TBps": round(b_out / (t_o * 1e-3) / 1e12, 3),
             "attach_TBps": round(b_att / (t_a * 1e-3) / 1e12, 3),
         }
+        if w is not None:
+            t_w, n_w = window_ms(lambda: eng.attach_scores(leaves, cost, tau, new_leaf=new,
+                                                           dp=f.dp, outside=out, weights=w),
+                                 a.window)
+            line["calls"]["attach_weighted"] = n_w
+            line["attach_weighted_ms"] = round(t_w, 4)
+            line["weighted_over_unweighted"] = round(t_w / t_a, 4)
         lines.append(line)
     # information only: one whole stepwise addition, host work included
     align = leaves[0].contiguous()

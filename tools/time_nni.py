@@ -2,7 +2,7 @@
 kernel against what they replace, one forward per neighbour.
 
     python tools/time_nni.py [--trees 1024] [--taxa 32] [--sites 5000] [--states 4]
-                             [--window 0.5] [--out FILE]
+                             [--window 0.5] [--weights] [--out FILE]
 
 Device events around windows of >= --window seconds of back-to-back launches,
 after the clocks have settled (blocks of forwards until one is within 1 % of
@@ -10,7 +10,9 @@ the one before, as bench.py does) and a warm-up of every kernel.  Per tau
 (0 and 0.5) one JSON line: forward_ms, outside_ms, nni_ms, bruteforce_ms =
 n_neighbours x forward_ms (the forward kernel scoring every neighbour as a
 tree of its own, measured in the same run), the bytes each pass moves by the
-shapes (no cache reuse assumed) and the bytes/s that gives.
+shapes (no cache reuse assumed) and the bytes/s that gives.  --weights also
+times nni_scores with uniform(0.25, 2) site weights next to the unweighted
+call: nni_weighted_ms and weighted_over_unweighted.
 """
 import argparse
 import json
@@ -89,6 +91,8 @@ def main():
     ap.add_argument("--sites", type=int, default=5000)
     ap.add_argument("--states", type=int, default=4)
     ap.add_argument("--window", type=float, default=0.5)
+    ap.add_argument("--weights", action="store_true",
+                    help="also time the weighted call (trex_sankoff_nni_w)")
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
@@ -97,6 +101,11 @@ def main():
     eng = SankoffEngine(plan, L, Q, dev)
     n_nb = 2 * (n - 2)
     b_out, b_nni = pass_bytes(plan, L, Q)
+    w = None
+    if a.weights:
+        g = torch.Generator(device=dev)
+        g.manual_seed(7)
+        w = torch.rand((B, L), generator=g, device=dev) * 1.75 + 0.25
     lines = []
     settled = None
     for tau in (0.0, 0.5):
@@ -125,6 +134,12 @@ def main():
             "outside_TBps": round(b_out / (t_o * 1e-3) / 1e12, 3),
             "nni_TBps": round(b_nni / (t_n * 1e-3) / 1e12, 3),
         }
+        if w is not None:
+            t_w, n_w = window_ms(lambda: eng.nni_scores(leaves, cost, tau, dp=f.dp, outside=out,
+                                                        weights=w), a.window)
+            line["calls"]["nni_weighted"] = n_w
+            line["nni_weighted_ms"] = round(t_w, 4)
+            line["weighted_over_unweighted"] = round(t_w / t_n, 4)
         print(json.dumps(line))
         lines.append(line)
     if a.out:

@@ -17,10 +17,17 @@ from .sankoff import (  # noqa: F401
     vmapped_backtrack,
 )
 from .search import (  # noqa: F401
+    BootstrapResult,
     HillClimbResult,
+    RatchetResult,
     SearchResult,
     StepwiseResult,
+    bootstrap_search,
+    bootstrap_weights,
+    clade_support,
+    compress_sites,
     nni_hill_climb,
+    parsimony_ratchet,
     parsimony_search,
     stepwise_addition,
 )
@@ -40,5 +47,6 @@ __all__ = [
     "sankoff_value_and_grad", "TreePlan", "children_from_adjacency",
     "create_balanced_binary_tree", "random_topologies", "apply_nni", "nni_hill_climb",
     "HillClimbResult", "insert_leaf", "relabel_leaves", "stepwise_addition", "StepwiseResult",
-    "parsimony_search", "SearchResult",
+    "parsimony_search", "SearchResult", "compress_sites", "parsimony_ratchet", "RatchetResult",
+    "bootstrap_weights", "bootstrap_search", "BootstrapResult", "clade_support",
 ]

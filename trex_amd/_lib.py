@@ -63,6 +63,12 @@ SIGNATURES = {
     "trex_attach_workspace_bytes": (_c_i64, [_c_i, _c_i, _c_i, _c_i]),
     "trex_sankoff_attach": (_c_i, [_p, _p, _p, _c_i, _c_i, _c_i, _c_i, _c_f, _p, _p, _p, _p, _p,
                                    _p, _c_i64, _p]),
+    # site weights (OPTIONAL below): weights after the last input table
+    "trex_site_weighted_sum": (_c_i, [_p, _p, _c_i, _c_i, _p, _p]),
+    "trex_sankoff_nni_w": (_c_i, [_p, _p, _p, _c_i, _c_i, _c_i, _c_i, _c_f, _p, _p, _p, _p, _p,
+                                  _c_i64, _p]),
+    "trex_sankoff_attach_w": (_c_i, [_p, _p, _p, _c_i, _c_i, _c_i, _c_i, _c_f, _p, _p, _p, _p, _p,
+                                     _p, _p, _c_i64, _p]),
     # multi-GPU exchange (RCCL, dlopen'ed on first use)
     "trex_comm_unique_id_bytes": (_c_i, []),
     "trex_comm_get_unique_id": (_c_i, [_p]),
@@ -159,13 +165,20 @@ SIGNATURES = {
 
 # entry points added without a version bump: a library named by TREX_HIP_LIB
 # may be an older v10 build without them (tools/ab.sh runs a parent commit's
-# library under this package); has_fused4() tells
-OPTIONAL = ("trex_fused4_program_ints", "trex_fused4_program_build", "trex_sankoff_fwd_bwd_prog")
+# library under this package); has_fused4() and has_site_weights() tell
+_FUSED4 = ("trex_fused4_program_ints", "trex_fused4_program_build", "trex_sankoff_fwd_bwd_prog")
+_SITE_WEIGHTS = ("trex_site_weighted_sum", "trex_sankoff_nni_w", "trex_sankoff_attach_w")
+OPTIONAL = _FUSED4 + _SITE_WEIGHTS
 
 
 def has_fused4() -> bool:
     """The loaded library has the fused Q = 4 program entry points."""
-    return all(hasattr(lib(), name) for name in OPTIONAL)
+    return all(hasattr(lib(), name) for name in _FUSED4)
+
+
+def has_site_weights() -> bool:
+    """The loaded library has the site-weight entry points."""
+    return all(hasattr(lib(), name) for name in _SITE_WEIGHTS)
 
 
 class TrexError(RuntimeError):

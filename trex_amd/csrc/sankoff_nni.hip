@@ -20,9 +20,12 @@
 // is the stabilised form (row minimum subtracted).  Neighbour scores are
 // summed over a wave's sites in fp64 (fixed butterfly), the per-wave partials
 // over a tree's tiles in a fixed order by a second kernel: no float atomics,
-// bitwise reproducible.  The attachment scores further down (a new leaf or a
-// subtree's row on every edge of a tree; DESIGN.md "Attachment scores") read
-// the same two tables with the same helpers.
+// bitwise reproducible.  With site weights (DESIGN.md "Site weights") a site's
+// score is multiplied by its weight in fp64 where it enters that sum and
+// nowhere else; the WT = false instantiations are the unweighted code.  The
+// attachment scores further down (a new leaf or a subtree's row on every edge
+// of a tree; DESIGN.md "Attachment scores") read the same two tables with the
+// same helpers.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -195,15 +198,29 @@ __global__ __launch_bounds__(kWave) void nni_outside_kernel(const NniArgs A) {
   }
 }
 
+// The lane's site weight as the fp64 factor of its site scores: one coalesced
+// 256-byte read per wave at the clamped site.  A tail lane holds the last
+// site's weight and is masked by a select where the sums are taken, so it adds
+// nothing whatever that weight is.  Unweighted: exactly 1.0 (x * 1.0 is exact).
+// The weights ([B][L], or null) are a kernel argument of their own behind the
+// argument record, so the WT = false kernels read the record they always read.
+template <bool WT>
+__device__ __forceinline__ double site_weight(const float* weights, int b, int L, int site) {
+  if constexpr (WT) return (double)weights[(size_t)b * L + site];
+  else return 1.0;
+}
+
 // Neighbour scores: per non-root internal v both moves' site scores, summed
 // over the wave's sites in fp64; lane 0 writes the two partials.
-template <int QP, bool DYN, bool SOFT>
-__global__ __launch_bounds__(kWave) void nni_score_kernel(const NniArgs A) {
+template <int QP, bool DYN, bool SOFT, bool WT>
+__global__ __launch_bounds__(kWave) void nni_score_kernel(const NniArgs A,
+                                                          const float* weights) {
   const int lane = threadIdx.x;
   const int b = blockIdx.x / A.tiles, tile = blockIdx.x % A.tiles;
   const int l = tile * kWave + lane;
   const bool on = l < A.L;
   const int site = on ? l : A.L - 1;
+  const double w = site_weight<WT>(weights, b, A.L, site);
   CostM<QP, DYN> cm;
   cm.load(A.cost, A.Q);
   const size_t tree = (size_t)b * A.ni * A.L * A.Q;
@@ -235,8 +252,8 @@ __global__ __launch_bounds__(kWave) void nni_score_kernel(const NniArgs A) {
       for (int i = 0; i < QP; ++i) x[i] = ou[i] + (k == 0 ? m0[i] : m1[i]) + mdv[i];
       sc[k] = oplus<QP, DYN, SOFT>(cm, A.a, A.bcoef, x);
     }
-    const double s0 = wave_sum_lane0(on ? (double)sc[0] : 0.0);
-    const double s1 = wave_sum_lane0(on ? (double)sc[1] : 0.0);
+    const double s0 = wave_sum_lane0(on ? (double)sc[0] * w : 0.0);
+    const double s1 = wave_sum_lane0(on ? (double)sc[1] * w : 0.0);
     if (lane == 0) {
       part[2 * e] = s0;
       part[2 * e + 1] = s1;
@@ -293,25 +310,33 @@ void nni_fill(NniArgs& A, const int32_t* nni_plan, const int8_t* leaves, const f
   tau_coefs(tau, &A.a, &A.bcoef);
 }
 
-template <bool SCORE, int QP, bool DYN>
-void nni_launch_q(bool soft, hipStream_t st, const NniArgs& A) {
+template <int QP, bool DYN, bool SOFT>
+void nni_score_launch(hipStream_t st, const NniArgs& A, const float* w) {
   const dim3 grid(A.B * A.tiles), block(kWave);
+  if (w) hipLaunchKernelGGL((nni_score_kernel<QP, DYN, SOFT, true>), grid, block, 0, st, A, w);
+  else hipLaunchKernelGGL((nni_score_kernel<QP, DYN, SOFT, false>), grid, block, 0, st, A, w);
+}
+
+template <bool SCORE, int QP, bool DYN>
+void nni_launch_q(bool soft, hipStream_t st, const NniArgs& A, const float* w) {
   if constexpr (SCORE) {
-    if (soft) hipLaunchKernelGGL((nni_score_kernel<QP, DYN, true>), grid, block, 0, st, A);
-    else hipLaunchKernelGGL((nni_score_kernel<QP, DYN, false>), grid, block, 0, st, A);
+    if (soft) nni_score_launch<QP, DYN, true>(st, A, w);
+    else nni_score_launch<QP, DYN, false>(st, A, w);
   } else {
+    const dim3 grid(A.B * A.tiles), block(kWave);
     if (soft) hipLaunchKernelGGL((nni_outside_kernel<QP, DYN, true>), grid, block, 0, st, A);
     else hipLaunchKernelGGL((nni_outside_kernel<QP, DYN, false>), grid, block, 0, st, A);
   }
 }
 
+// w: the scoring kernel's site weights, or null (the outside pass has none)
 template <bool SCORE>
-void nni_launch(bool soft, hipStream_t st, const NniArgs& A) {
+void nni_launch(bool soft, hipStream_t st, const NniArgs& A, const float* w = nullptr) {
   switch (A.Q) {
-    case 2: nni_launch_q<SCORE, 2, false>(soft, st, A); break;
-    case 3: nni_launch_q<SCORE, 3, false>(soft, st, A); break;
-    case 4: nni_launch_q<SCORE, 4, false>(soft, st, A); break;
-    default: nni_launch_q<SCORE, kNniPadQ, true>(soft, st, A); break;
+    case 2: nni_launch_q<SCORE, 2, false>(soft, st, A, w); break;
+    case 3: nni_launch_q<SCORE, 3, false>(soft, st, A, w); break;
+    case 4: nni_launch_q<SCORE, 4, false>(soft, st, A, w); break;
+    default: nni_launch_q<SCORE, kNniPadQ, true>(soft, st, A, w); break;
   }
 }
 
@@ -334,14 +359,16 @@ __device__ __forceinline__ int desc_node(int desc, int nl) {
 // A wave walks its tree's internal rows p: both child edges of p from O_p and
 // the children's messages, on the root row also the new-root entry; site sums
 // in fp64, lane 0 writes the partials at the edges' lower node ids.
-template <int QP, bool DYN, bool SOFT>
-__global__ __launch_bounds__(kWave) void attach_score_kernel(const AttachArgs AA) {
+template <int QP, bool DYN, bool SOFT, bool WT>
+__global__ __launch_bounds__(kWave) void attach_score_kernel(const AttachArgs AA,
+                                                             const float* weights) {
   const NniArgs& A = AA.n;
   const int lane = threadIdx.x;
   const int b = blockIdx.x / A.tiles, tile = blockIdx.x % A.tiles;
   const int l = tile * kWave + lane;
   const bool on = l < A.L;
   const int site = on ? l : A.L - 1;
+  const double w = site_weight<WT>(weights, b, A.L, site);
   CostM<QP, DYN> cm;
   cm.load(A.cost, A.Q);
   const size_t tree = (size_t)b * A.ni * A.L * A.Q;
@@ -386,8 +413,8 @@ __global__ __launch_bounds__(kWave) void attach_score_kernel(const AttachArgs AA
       for (int i = 0; i < QP; ++i) x[i] = op[i] + (k == 0 ? m1[i] : m0[i]) + mdw[i];
       sc[k] = oplus<QP, DYN, SOFT>(cm, A.a, A.bcoef, x);
     }
-    const double s0 = wave_sum_lane0(on ? (double)sc[0] : 0.0);
-    const double s1 = wave_sum_lane0(on ? (double)sc[1] : 0.0);
+    const double s0 = wave_sum_lane0(on ? (double)sc[0] * w : 0.0);
+    const double s1 = wave_sum_lane0(on ? (double)sc[1] * w : 0.0);
     if (lane == 0) {
       part[desc_node(e.y, A.nl)] = s0;
       part[desc_node(e.z, A.nl)] = s1;
@@ -399,25 +426,31 @@ __global__ __launch_bounds__(kWave) void attach_score_kernel(const AttachArgs AA
 #pragma unroll
       for (int i = 0; i < QP; ++i) x[i] = m0[i] + mn[i];
       const float sr = oplus<QP, DYN, SOFT>(cm, A.a, A.bcoef, x);
-      const double s2 = wave_sum_lane0(on ? (double)sr : 0.0);
+      const double s2 = wave_sum_lane0(on ? (double)sr * w : 0.0);
       if (lane == 0) part[A.nl + e.x] = s2;
     }
   }
 }
 
-template <int QP, bool DYN>
-void attach_launch_q(bool soft, hipStream_t st, const AttachArgs& A) {
+template <int QP, bool DYN, bool SOFT>
+void attach_score_launch(hipStream_t st, const AttachArgs& A, const float* w) {
   const dim3 grid(A.n.B * A.n.tiles), block(kWave);
-  if (soft) hipLaunchKernelGGL((attach_score_kernel<QP, DYN, true>), grid, block, 0, st, A);
-  else hipLaunchKernelGGL((attach_score_kernel<QP, DYN, false>), grid, block, 0, st, A);
+  if (w) hipLaunchKernelGGL((attach_score_kernel<QP, DYN, SOFT, true>), grid, block, 0, st, A, w);
+  else hipLaunchKernelGGL((attach_score_kernel<QP, DYN, SOFT, false>), grid, block, 0, st, A, w);
 }
 
-void attach_launch(bool soft, hipStream_t st, const AttachArgs& A) {
+template <int QP, bool DYN>
+void attach_launch_q(bool soft, hipStream_t st, const AttachArgs& A, const float* w) {
+  if (soft) attach_score_launch<QP, DYN, true>(st, A, w);
+  else attach_score_launch<QP, DYN, false>(st, A, w);
+}
+
+void attach_launch(bool soft, hipStream_t st, const AttachArgs& A, const float* w) {
   switch (A.n.Q) {
-    case 2: attach_launch_q<2, false>(soft, st, A); break;
-    case 3: attach_launch_q<3, false>(soft, st, A); break;
-    case 4: attach_launch_q<4, false>(soft, st, A); break;
-    default: attach_launch_q<kNniPadQ, true>(soft, st, A); break;
+    case 2: attach_launch_q<2, false>(soft, st, A, w); break;
+    case 3: attach_launch_q<3, false>(soft, st, A, w); break;
+    case 4: attach_launch_q<4, false>(soft, st, A, w); break;
+    default: attach_launch_q<kNniPadQ, true>(soft, st, A, w); break;
   }
 }
 
@@ -446,11 +479,12 @@ extern "C" int64_t trex_nni_workspace_bytes(int B, int L, int n_all, int Q) {
   return (int64_t)B * ((L + kWave - 1) / kWave) * (ni - 1) * 2 * 8 + 256;
 }
 
-extern "C" int trex_sankoff_nni(const int32_t* nni_plan, const int8_t* leaves, const float* cost,
-                                int B, int L, int n_all, int Q, float tau, const float* dp,
-                                const float* outside, float* nni_score, void* workspace,
-                                int64_t workspace_bytes, void* stream) {
-  const char* fn = "trex_sankoff_nni";
+namespace {
+
+int nni_run(const char* fn, const int32_t* nni_plan, const int8_t* leaves, const float* cost,
+            int B, int L, int n_all, int Q, float tau, const float* dp, const float* outside,
+            const float* weights, float* nni_score, void* workspace, int64_t workspace_bytes,
+            void* stream) {
   if (int e = nni_check_shape(fn, B, L, n_all, Q, tau)) return e;
   if (!nni_plan || !leaves || !cost || !dp || !outside || !nni_score || !workspace)
     return set_error(TREX_E_ARG, "%s: null pointer argument", fn);
@@ -460,7 +494,7 @@ extern "C" int trex_sankoff_nni(const int32_t* nni_plan, const int8_t* leaves, c
   nni_fill(A, nni_plan, leaves, cost, B, L, n_all, Q, tau, dp, const_cast<float*>(outside));
   A.part = static_cast<double*>(workspace);
   hipStream_t st = (hipStream_t)stream;
-  nni_launch<true>(tau > 0.0f, st, A);
+  nni_launch<true>(tau > 0.0f, st, A, weights);
   if (int e = hip_check(fn)) return e;
   const int moves = (A.ni - 1) * 2;
   const int64_t n = (int64_t)B * moves;
@@ -469,17 +503,37 @@ extern "C" int trex_sankoff_nni(const int32_t* nni_plan, const int8_t* leaves, c
   return hip_check(fn);
 }
 
+}  // namespace
+
+extern "C" int trex_sankoff_nni_w(const int32_t* nni_plan, const int8_t* leaves,
+                                  const float* cost, int B, int L, int n_all, int Q, float tau,
+                                  const float* dp, const float* outside, const float* weights,
+                                  float* nni_score, void* workspace, int64_t workspace_bytes,
+                                  void* stream) {
+  return nni_run("trex_sankoff_nni_w", nni_plan, leaves, cost, B, L, n_all, Q, tau, dp, outside,
+                 weights, nni_score, workspace, workspace_bytes, stream);
+}
+
+extern "C" int trex_sankoff_nni(const int32_t* nni_plan, const int8_t* leaves, const float* cost,
+                                int B, int L, int n_all, int Q, float tau, const float* dp,
+                                const float* outside, float* nni_score, void* workspace,
+                                int64_t workspace_bytes, void* stream) {
+  return nni_run("trex_sankoff_nni", nni_plan, leaves, cost, B, L, n_all, Q, tau, dp, outside,
+                 nullptr, nni_score, workspace, workspace_bytes, stream);
+}
+
 extern "C" int64_t trex_attach_workspace_bytes(int B, int L, int n_all, int Q) {
   if (B <= 0 || L <= 0 || n_all < 5 || n_all % 2 == 0 || Q < 2 || Q > kSiteMaxQ) return 0;
   return (int64_t)B * ((L + kWave - 1) / kWave) * n_all * 8 + 256;
 }
 
-extern "C" int trex_sankoff_attach(const int32_t* attach_plan, const int8_t* leaves,
-                                   const float* cost, int B, int L, int n_all, int Q, float tau,
-                                   const float* dp, const float* outside, const int8_t* sub_codes,
-                                   const float* sub_rows, float* attach_score, void* workspace,
-                                   int64_t workspace_bytes, void* stream) {
-  const char* fn = "trex_sankoff_attach";
+namespace {
+
+int attach_run(const char* fn, const int32_t* attach_plan, const int8_t* leaves,
+               const float* cost, int B, int L, int n_all, int Q, float tau, const float* dp,
+               const float* outside, const int8_t* sub_codes, const float* sub_rows,
+               const float* weights, float* attach_score, void* workspace,
+               int64_t workspace_bytes, void* stream) {
   if (int e = nni_check_shape(fn, B, L, n_all, Q, tau)) return e;
   if (!attach_plan || !leaves || !cost || !dp || !outside || !attach_score || !workspace)
     return set_error(TREX_E_ARG, "%s: null pointer argument", fn);
@@ -493,10 +547,33 @@ extern "C" int trex_sankoff_attach(const int32_t* attach_plan, const int8_t* lea
   A.sub_codes = sub_codes;
   A.sub_rows = sub_rows;
   hipStream_t st = (hipStream_t)stream;
-  attach_launch(tau > 0.0f, st, A);
+  attach_launch(tau > 0.0f, st, A, weights);
   if (int e = hip_check(fn)) return e;
   const int64_t n = (int64_t)B * n_all;
   hipLaunchKernelGGL(nni_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
                      A.n.part, B, A.n.tiles, n_all, attach_score);
   return hip_check(fn);
+}
+
+}  // namespace
+
+extern "C" int trex_sankoff_attach_w(const int32_t* attach_plan, const int8_t* leaves,
+                                     const float* cost, int B, int L, int n_all, int Q, float tau,
+                                     const float* dp, const float* outside,
+                                     const int8_t* sub_codes, const float* sub_rows,
+                                     const float* weights, float* attach_score, void* workspace,
+                                     int64_t workspace_bytes, void* stream) {
+  return attach_run("trex_sankoff_attach_w", attach_plan, leaves, cost, B, L, n_all, Q, tau, dp,
+                    outside, sub_codes, sub_rows, weights, attach_score, workspace,
+                    workspace_bytes, stream);
+}
+
+extern "C" int trex_sankoff_attach(const int32_t* attach_plan, const int8_t* leaves,
+                                   const float* cost, int B, int L, int n_all, int Q, float tau,
+                                   const float* dp, const float* outside, const int8_t* sub_codes,
+                                   const float* sub_rows, float* attach_score, void* workspace,
+                                   int64_t workspace_bytes, void* stream) {
+  return attach_run("trex_sankoff_attach", attach_plan, leaves, cost, B, L, n_all, Q, tau, dp,
+                    outside, sub_codes, sub_rows, nullptr, attach_score, workspace,
+                    workspace_bytes, stream);
 }

@@ -137,12 +137,65 @@ class SankoffEngine:
             if not t.is_contiguous() or t.device != self.device:
                 raise ValueError("inputs must be contiguous tensors on the engine's device")
 
+    def _check_weights(self, weights):
+        """Site weights: a contiguous float32 (B, L) tensor on the engine's
+        device, one row per tree.  Values are not read here (nothing
+        synchronises): they must be finite, and scores carry the kernels'
+        relative bar only when they are >= 0."""
+        from ._lib import has_site_weights
+
+        torch = _torch()
+        shape = (self.plan.B, self.L)
+        if (not hasattr(weights, "dtype") or weights.dtype != torch.float32
+                or tuple(weights.shape) != shape or not weights.is_contiguous()
+                or weights.device != self.device):
+            raise ValueError(f"weights must be a contiguous float32 {shape} tensor on the "
+                             "engine's device")
+        if not has_site_weights():
+            raise RuntimeError(f"{lib()._name} has no site-weight entry points "
+                               "(trex_site_weighted_sum, trex_sankoff_nni_w, "
+                               "trex_sankoff_attach_w): rebuild libtrexhip.so")
+
     # -- kernels -----------------------------------------------------------
+    def weighted_score(self, site_score, weights, out=None):
+        """(B,) float32 ``sum_l weights[b, l] * site_score[b, l]`` of a
+        forward's ``site_score`` (B, L): products and sum in fp64 in a fixed
+        order, rounded once; repeated calls are bitwise equal.  Weights are
+        finite; the relative bar of the site scores carries over only when
+        they are >= 0."""
+        torch = _torch()
+        self._check_weights(weights)
+        B = self.plan.B
+        if (not hasattr(site_score, "dtype") or site_score.dtype != torch.float32
+                or tuple(site_score.shape) != (B, self.L) or not site_score.is_contiguous()
+                or site_score.device != self.device):
+            raise ValueError(f"site_score must be a contiguous float32 {(B, self.L)} tensor on "
+                             "the engine's device")
+        if out is None:
+            out = torch.empty((B,), dtype=torch.float32, device=self.device)
+        elif (out.dtype != torch.float32 or tuple(out.shape) != (B,) or not out.is_contiguous()
+              or out.device != self.device):
+            raise ValueError(f"out must be a contiguous float32 {(B,)} tensor on the engine's "
+                             "device")
+        check(lib().trex_site_weighted_sum(ptr(site_score), ptr(weights), B, self.L, ptr(out),
+                                           stream_handle(self.device)))
+        return out
+
     def forward(self, leaves, cost, tau: float = 0.0, *, dp=True, site_score=False,
-                hard_root=False, out=None) -> ForwardResult:
-        """Post-order DP (sankoff.py:24-97) + per-tree total (sankoff.py:187)."""
+                hard_root=False, out=None, weights=None) -> ForwardResult:
+        """Post-order DP (sankoff.py:24-97) + per-tree total (sankoff.py:187).
+
+        ``weights`` (float32 (B, L), finite): ``tree_score`` is the weighted
+        total ``sum_l weights[b, l] * site_score[b, l]`` (``weighted_score``)
+        and ``site_score`` is returned too; the DP table is per site and does
+        not depend on the weights.  ``hard_root`` keeps its meaning: it
+        selects how each site's score is taken from the root row, and the
+        weighted total is the weighted sum of those site scores."""
         torch = _torch()
         self._check_inputs(leaves, cost)
+        if weights is not None:
+            self._check_weights(weights)
+            site_score = True
         p = self.plan
         o = out or {}
         if dp is True:
@@ -166,6 +219,8 @@ class SankoffEngine:
             ptr(self.plan_dev), p.slot_word, ptr(leaves), ptr(cost), p.B, self.L, p.n_all,
             self.Q, float(tau), flags, ptr(dp_t), ptr(ss), ptr(ts), ptr(self.workspace),
             self.workspace.numel(), stream_handle(self.device)))
+        if weights is not None:
+            self.weighted_score(ss, weights, out=ts)
         return ForwardResult(ts, dp_t, ss)
 
     def backward(self, leaves, cost, tau: float, dp, d_tree_score=None, *, marginals=False,
@@ -272,13 +327,19 @@ class SankoffEngine:
             float(tau), ptr(dp), ptr(out), stream_handle(self.device)))
         return out
 
-    def nni_scores(self, leaves, cost, tau: float = 0.0, *, dp=None, outside=None):
+    def nni_scores(self, leaves, cost, tau: float = 0.0, *, dp=None, outside=None, weights=None):
         """Tree scores of all NNI neighbours, float32 (B, n_int - 1, 2): entry
         [b, v - n_leaves, k] is tree b after ``apply_nni(children[b], v, k)``
         (plain score: no hard_root).  Runs the forward and / or the outside
-        pass when ``dp`` / ``outside`` are not given."""
+        pass when ``dp`` / ``outside`` are not given.  ``weights`` (float32
+        (B, L), finite): every site's move score is multiplied by its weight
+        in fp64 where the sites are summed; the tables stay unweighted.
+        All-ones weights give the bits of the unweighted call; the relative
+        bar holds only for weights >= 0."""
         torch = _torch()
         self._check_inputs(leaves, cost)
+        if weights is not None:
+            self._check_weights(weights)
         p = self.plan
         if dp is None:
             if outside is not None:
@@ -293,23 +354,29 @@ class SankoffEngine:
         if ws is None or ws.numel() < max(nbytes, 1):
             ws = self._nni_ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=self.device)
         score = torch.empty((p.B, p.n_int - 1, 2), dtype=torch.float32, device=self.device)
-        check(lib().trex_sankoff_nni(
-            ptr(p.nni_device(self.device)), ptr(leaves), ptr(cost), p.B, self.L, p.n_all, self.Q,
-            float(tau), ptr(dp), ptr(outside), ptr(score), ptr(ws), ws.numel(),
-            stream_handle(self.device)))
+        head = (ptr(p.nni_device(self.device)), ptr(leaves), ptr(cost), p.B, self.L, p.n_all,
+                self.Q, float(tau), ptr(dp), ptr(outside))
+        tail = (ptr(score), ptr(ws), ws.numel(), stream_handle(self.device))
+        if weights is None:  # also what an older library under TREX_HIP_LIB has
+            check(lib().trex_sankoff_nni(*head, *tail))
+        else:
+            check(lib().trex_sankoff_nni_w(*head, ptr(weights), *tail))
         return score
 
     def attach_scores(self, leaves, cost, tau: float = 0.0, *, new_leaf=None, sub_rows=None,
-                      dp=None, outside=None):
+                      dp=None, outside=None, weights=None):
         """Tree scores after attaching a subtree on every edge, float32
         (B, n_all): entry [b, x] is tree b with the subtree on the edge above
         node x (``insert_leaf(children[b], x)`` for a leaf; x = n_all - 1 is a
         new root; plain score).  The subtree is ``new_leaf``, int8 (B, L) leaf
         codes, or ``sub_rows``, float32 (B, L, Q) inside rows (a subtree's
         root DP row).  Runs the forward and / or the outside pass when ``dp``
-        / ``outside`` are not given."""
+        / ``outside`` are not given.  ``weights`` (float32 (B, L), finite):
+        site weights as in ``nni_scores``."""
         torch = _torch()
         self._check_inputs(leaves, cost)
+        if weights is not None:
+            self._check_weights(weights)
         p = self.plan
         if (new_leaf is None) == (sub_rows is None):
             raise ValueError("give exactly one of new_leaf and sub_rows")
@@ -333,10 +400,13 @@ class SankoffEngine:
             ws = self._attach_ws = torch.empty(max(nbytes, 1), dtype=torch.uint8,
                                                device=self.device)
         score = torch.empty((p.B, p.n_all), dtype=torch.float32, device=self.device)
-        check(lib().trex_sankoff_attach(
-            ptr(p.attach_device(self.device)), ptr(leaves), ptr(cost), p.B, self.L, p.n_all,
-            self.Q, float(tau), ptr(dp), ptr(outside), ptr(new_leaf), ptr(sub_rows), ptr(score),
-            ptr(ws), ws.numel(), stream_handle(self.device)))
+        head = (ptr(p.attach_device(self.device)), ptr(leaves), ptr(cost), p.B, self.L, p.n_all,
+                self.Q, float(tau), ptr(dp), ptr(outside), ptr(new_leaf), ptr(sub_rows))
+        tail = (ptr(score), ptr(ws), ws.numel(), stream_handle(self.device))
+        if weights is None:
+            check(lib().trex_sankoff_attach(*head, *tail))
+        else:
+            check(lib().trex_sankoff_attach_w(*head, ptr(weights), *tail))
         return score
 
     def value_and_grad(self, leaves, cost, tau: float = 0.0, d_tree_score=None,
