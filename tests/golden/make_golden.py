@@ -5,9 +5,11 @@ The reference (JAX) cannot be imported in this image, so the fixtures are:
     fixtures (tests/test_sankoff.py:9-72; derivation in SURVEY.md §4) and the
     tie-averaged gradient derived by hand for the same tree (DESIGN.md);
   * sankoff_cases.npz -- oracle outputs on seeded inputs, pinned so later
-    oracle edits cannot drift silently (tests/test_oracle.py re-derives them).
+    oracle edits cannot drift silently (tests/test_oracle.py re-derives them);
+  * plan_cases.npz -- what the built library's host planner returns on a
+    corpus of child lists (needs libtrexhip.so; `plan` writes this one alone).
 
-    python tests/golden/make_golden.py
+    python tests/golden/make_golden.py [plan]
 """
 
 from __future__ import annotations
@@ -23,7 +25,8 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-from _cases import int_cost, random_leaves, random_topologies, weird_children  # noqa: E402
+from _cases import (balanced_children, int_cost, random_leaves, random_topologies,  # noqa: E402
+                    weird_children)
 from oracle.sankoff_ref import run_sankoff_ref  # noqa: E402
 from oracle.softmin_ref import batched_fwd_bwd_ref  # noqa: E402
 from trex_amd.topology import adjacency_from_children  # noqa: E402
@@ -112,7 +115,72 @@ def compute(ch, leaves, cost):
     return res
 
 
+def plan_corpus():
+    """Child lists for the planner fixture: uniform batches by name, and
+    ragged batches by name as (list of per-tree child lists, site counts)."""
+    u = {f"random{nl}": random_topologies(3, nl, seed=nl) for nl in (3, 4, 8, 16, 40, 64)}
+    u["balanced64"] = balanced_children(64, B=2)
+    n = 33  # a caterpillar: every internal child is the previous step
+    cat = np.full((1, 2 * n - 1, 2), -1, np.int32)
+    cat[0, n] = (0, 1)
+    for k in range(1, n - 1):
+        cat[0, n + k] = (k + 1, n + k - 1)
+    u["caterpillar33"] = cat
+    for kind in ("fwdref", "dag", "cycle"):
+        u[kind] = weird_children(kind)[None]
+    # test_plan_deferred_cherries' tree: 13 an orphan, cherry 10 with two parents
+    u["unreached"] = balanced_children(8).copy()
+    u["unreached"][0, 14] = (12, 10)
+    # row 8 a child of 11 and of 12, every row reached (leaf 7 is unused)
+    u["shared"] = balanced_children(8).copy()
+    u["shared"][0, 11] = (6, 8)
+    u["n_all3"] =np.array([[[-1, -1], [-1, -1], [0, 1]]], np.int32)  # 2 leaves
+    u["n_all4"] = np.array([[[-1, -1], [-1, -1], [0, 1], [1, 2]]], np.int32)  # even
+    u["malformed"] = balanced_children(8).copy()
+    u["malformed"][0, 9, 0] = 99
+    r = {
+        "a": ([u["random3"][0], u["random8"][1], u["random40"][2], u["fwdref"][0],
+               u["balanced64"][0]], [1, 64, 65, 7, 130]),
+        "b": ([u["dag"][0], u["cycle"][0], u["unreached"][0], u["caterpillar33"][0],
+               u["n_all3"][0], u["random16"][0], u["random64"][0]],
+              [65, 1, 64, 200, 5, 64, 1000]),
+        "malformed": ([u["random4"][0], u["malformed"][0]], [3, 3]),
+        "no_sites": ([u["random4"][0]], [0]),
+    }
+    return u, r
+
+
+def plan_main():
+    """plan_cases.npz: the host planner's output (trex_amd/csrc/plan.cpp) on
+    the corpus above, with TREX_DEFER unset and "0".  It pins the plan format
+    bit for bit: regenerate it only with a deliberate format change (and a
+    trex_version() bump).  tests/test_plan_golden_cpu.py rebuilds every case."""
+    from _plan_golden import ints_table, run_ragged, run_uniform
+
+    uniform, ragged = plan_corpus()
+    arrays = {"ints": ints_table()}
+    for name, ch in uniform.items():
+        arrays[f"u/{name}/children"] = ch
+        for defer in (True, False):
+            for key, val in run_uniform(ch, defer).items():
+                arrays[f"u/{name}/{'defer' if defer else 'nodefer'}/{key}"] = val
+    for name, (trees, sites) in ragged.items():
+        arrays[f"r/{name}/children"] = np.concatenate(trees, axis=0)
+        arrays[f"r/{name}/n_all"] = np.array([len(t) for t in trees], np.int32)
+        arrays[f"r/{name}/sites"] = np.array(sites, np.int32)
+        for defer in (True, False):
+            out = run_ragged(arrays[f"r/{name}/children"], arrays[f"r/{name}/n_all"],
+                             arrays[f"r/{name}/sites"], defer)
+            for key, val in out.items():
+                arrays[f"r/{name}/{'defer' if defer else 'nodefer'}/{key}"] = val
+    np.savez_compressed(os.path.join(HERE, "plan_cases.npz"), **arrays)
+    print("wrote plan_cases.npz:", len(uniform), "uniform,", len(ragged), "ragged batches")
+
+
 def main():
+    if sys.argv[1:] == ["plan"]:  # the planner fixture alone
+        return plan_main()
+    plan_main()
     with open(os.path.join(HERE, "kat_sankoff.json"), "w") as f:
         json.dump(KAT, f, indent=1)
     arrays = {}

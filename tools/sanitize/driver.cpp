@@ -3,7 +3,9 @@
 //   * trex_amd/csrc/plan.cpp -- the topology planner (uniform and ragged
 //     batches) on random, quirky (-1 fills, forward references, DAGs,
 //     orphans), cyclic and malformed child lists, writing into buffers sized
-//     exactly by trex_plan_ints / trex_ragged_plan_ints, and the NNI planner
+//     exactly by trex_plan_ints / trex_ragged_plan_ints, the fused Q = 4
+//     program (trex_fused4_program_build) of every accepted uniform plan, its
+//     accepted records range-checked, and the NNI planner
 //     (trex_nni_plan_build) and the attach planner (trex_attach_plan_build) on
 //     the same trees, their accepted plans range-checked;
 //   * oracle/cpu_port.c -- the OpenMP C restatement (the CPU baseline and a
@@ -76,8 +78,34 @@ void perturb(int nl, int32_t* ch, int mode) {
   }
 }
 
+// the fused Q = 4 program of an accepted plan, into a buffer of exactly
+// trex_fused4_program_ints; an accepted program's records stay in range: rows
+// below ni, operand offsets inside the leaf tile / the slot stack
+int check_fused4(const std::vector<int32_t>& plan, int B, int n_all, int n_slots, int* built) {
+  const int nl = (n_all + 1) / 2, ni = n_all - nl;
+  const int64_t n = trex_fused4_program_ints(B, n_all);
+  if (n != TREX_PLAN_HEADER_INTS + (int64_t)B * ni * 8) return 20;
+  std::vector<int32_t> prog((size_t)n);
+  const int rc = trex_fused4_program_build(plan.data(), B, n_all, prog.data());
+  if (rc == TREX_E_UNSUPPORTED) return 0;  // a quirky tree: the generic kernel's
+  if (rc != 0) return 21;
+  ++*built;
+  for (int64_t t = 0; t < (int64_t)B * ni; ++t) {
+    const int32_t* r = prog.data() + TREX_PLAN_HEADER_INTS + 8 * t;
+    const bool leaf[2] = {(r[0] & 1) != 0, (r[0] & 2) != 0};  // kF4Leaf0 / kF4Leaf1
+    if (r[1] < 0 || r[1] >= ni) return 22;
+    for (int c = 0; c < 2; ++c) {
+      const int32_t lim = leaf[c] ? nl * 64 : n_slots * 1024;  // 0: kF4Prev* (bypass)
+      if (r[2 + c] < 0 || (r[2 + c] >= lim && r[2 + c] != 0)) return 23;
+      if (r[5 + c] != -1 && (leaf[c] || r[5 + c] < 0 || r[5 + c] >= ni)) return 24;
+    }
+    if (r[4] < 0 || (r[4] >= n_slots * 1024 && r[4] != 0)) return 25;
+  }
+  return 0;
+}
+
 int check_uniform() {
-  int runs = 0;
+  int runs = 0, fused = 0;
   for (int it = 0; it < 400; ++it) {
     const int nl = rnd(2, 128);
     const int n_all = 2 * nl - 1;
@@ -93,9 +121,11 @@ int check_uniform() {
     int32_t info[4];
     const int rc = trex_plan_build(ch.data(), B, n_all, plan.data(), info);
     if (rc != 0 && rc != TREX_E_TOPOLOGY && rc != TREX_E_ARG) return 1;
+    if (rc == 0)
+      if (int e = check_fused4(plan, B, n_all, info[0] & 0xFFFF, &fused)) return e;
     ++runs;
   }
-  std::printf("uniform plans: %d\n", runs);
+  std::printf("uniform plans: %d, fused Q = 4 programs: %d\n", runs, fused);
   return 0;
 }
 

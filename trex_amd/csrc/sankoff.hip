@@ -190,8 +190,8 @@ int check_shape(const char* fn, int B, int L, int n_all, int Q, Shape* sh) {
   sh->B = B;
   sh->L = L;
   sh->n_all = n_all;
-  sh->nl = (n_all + 1) / 2;
-  sh->ni = n_all - sh->nl;
+  sh->nl = tree_nl(n_all);
+  sh->ni = tree_ni(n_all);
   sh->Q = Q;
   return TREX_OK;
 }
@@ -438,12 +438,13 @@ int run_phase(const char* fn, int phase, const int32_t* plan, int n_slots, const
   if (flags & ~TREX_FLAG_HARD_ROOT) return set_error(TREX_E_ARG, "%s: unknown flags 0x%x", fn, flags);
   // n_slots is the plan's slot word: the stack depth in its low half (route)
   if ((n_slots & 0xFFFF) > 250) return set_error(TREX_E_ARG, "%s: bad n_slots", fn);
-  SankoffCall c = sankoff_call(phase, plan + TREX_PLAN_HEADER_INTS, leaves, cost, B, L, s.nl, s.ni,
-                               Q, n_slots & 0xFFFF, tau, flags, dp, site_score, tree_score, dts,
+  const PlanLayout lay = plan_layout(B, s.ni);
+  SankoffCall c = sankoff_call(phase, plan + lay.fwd, leaves, cost, B, L, s.nl, s.ni, Q,
+                               n_slots & 0xFFFF, tau, flags, dp, site_score, tree_score, dts,
                                d_cost, marg, anc, workspace, stream);
   const Route r = route(c, n_slots, prog != nullptr, workspace_bytes);
-  const int32_t* staged = plan + TREX_PLAN_HEADER_INTS + (int64_t)B * s.ni * 6;
-  const int32_t* lanes = staged + (int64_t)B * staged_tree_ints(s.ni);
+  const int32_t* staged = plan + lay.staged;
+  const int32_t* lanes = plan + lay.lanes;
   switch (r.family) {
     case Family::kBigq: return bigq_run(fn, c);
     case Family::kStaged: return staged_run(fn, c, staged);
@@ -488,7 +489,7 @@ extern "C" int64_t trex_workspace_bytes(int B, int L, int n_all, int Q) {
   if (Q > kWideMaxQ) return bigq_workspace_bytes(B, L, Q);
   if (Q > kSiteMaxQ) return wide_workspace_bytes(B, L, Q);
   if (Q > 4) {  // + the fused lane-per-site kernel's s rows
-    const int64_t ni = n_all - (n_all + 1) / 2;
+    const int64_t ni = tree_ni(n_all);
     return site_srow_offset(B, L, Q) + (int64_t)B * std::max<int64_t>(ni, 0) * L * Q * 4;
   }
   const int64_t nb = (int64_t)B * q4_tiles(L);
@@ -561,7 +562,7 @@ extern "C" int trex_sankoff_backtrack(const int32_t* plan, int backtrack_ok, con
                      "topology (cyclic child references)");
   if (!plan || !cost || !dp || !anc_states)
     return set_error(TREX_E_ARG, "trex_sankoff_backtrack: null pointer argument");
-  const int32_t* bt32 = plan + TREX_PLAN_HEADER_INTS + (int64_t)B * s.ni * 4;
+  const int32_t* bt32 = plan + plan_layout(B, s.ni).bt;
   if (Q > kWideMaxQ) return bigq_backtrack(bt32, cost, dp, B, L, s.ni, Q, anc_states, stream);
   // every uniform batch: the split-lane kernels of sankoff_wide.hip (4 lanes
   // per site for Q <= 4, 8 for Q <= 32, one lane per site for codons); ragged
@@ -573,7 +574,7 @@ extern "C" int trex_dp_to_trex_layout(const float* dp, const int8_t* leaves, int
                                       int n_all, int Q, float* out, void* stream) {
   if (B <= 0 || L <= 0 || n_all < 3 || Q < 2 || Q > kBigMaxQ || !dp || !leaves || !out)
     return set_error(TREX_E_ARG, "trex_dp_to_trex_layout: bad arguments");
-  const int nl = (n_all + 1) / 2;
+  const int nl = tree_nl(n_all);
   const size_t total = (size_t)B * n_all * L;
   const int grid = (int)std::min<size_t>((total + 255) / 256, 65536);
   hipLaunchKernelGGL(to_trex_layout_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, dp,
@@ -620,9 +621,10 @@ extern "C" int trex_sankoff_ragged(int phase, const int32_t* plan, int B, int n_
   if (n_slots < 0 || n_slots > 250) return set_error(TREX_E_ARG, "%s: bad n_slots", fn);
   if (flags & ~TREX_FLAG_HARD_ROOT) return set_error(TREX_E_ARG, "%s: unknown flags 0x%x", fn, flags);
   // the plan: per-tree records, the work-item -> tree table, the steps
-  const int* meta = plan + TREX_PLAN_HEADER_INTS;
-  const int* ritem = meta + (size_t)B * kRaggedMeta;
-  SankoffCall c = sankoff_call(phase, ritem + items, leaves, cost, B, 0, max_nl, max_nl - 1, Q,
+  const RaggedLayout lay = ragged_layout(B, items, 0);
+  const int* meta = plan + lay.meta;
+  const int* ritem = plan + lay.item;
+  SankoffCall c = sankoff_call(phase, plan + lay.fwd, leaves, cost, B, 0, max_nl, max_nl - 1, Q,
                                n_slots, tau, flags, dp, site_score, tree_score, d_tree_score,
                                d_cost, marginals, anc_states, workspace, stream);
   c.rmeta = meta;
@@ -650,7 +652,7 @@ extern "C" int trex_sankoff_ragged_backtrack(const int32_t* plan, int B, int64_t
                      "%s: the reference backtrack does not terminate on this batch (cyclic child "
                      "references)", fn);
   if (!plan || !cost || !dp || !anc_states) return set_error(TREX_E_ARG, "%s: null pointer", fn);
-  const int* meta = plan + TREX_PLAN_HEADER_INTS;
+  const int* meta = plan + ragged_layout(B, items, steps).meta;
   if (Q > kWideMaxQ) return bigq_ragged_backtrack(meta, B, items, steps, cost, dp, Q, anc_states, stream);
   if (Q > 4) return wide_ragged_backtrack(meta, B, items, steps, cost, dp, Q, anc_states, stream);
   hipStream_t st = (hipStream_t)stream;

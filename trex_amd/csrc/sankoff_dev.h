@@ -11,7 +11,6 @@ namespace {
 
 constexpr float kSentinel = 1e5f;  // sankoff.py:152
 constexpr int kWave = 64;
-constexpr int kKindLeaf = 1, kKindInt = 2;  // 0 = 1e5 sentinel row
 
 // Read-only, wave-uniform data (topology program, cost matrix) goes through
 // the constant address space so hipcc emits scalar loads (s_load): vector

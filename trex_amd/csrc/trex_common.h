@@ -13,10 +13,35 @@
 
 namespace trex {
 
-constexpr int32_t kPlanMagic = 0x54524558;  // 'TREX'
+// word 0 of the header of everything plan.cpp builds
+constexpr int32_t kPlanMagic = 0x54524558;    // 'TREX' trex_plan_build
+constexpr int32_t kF4Magic = 0x54524634;      // 'TRF4' trex_fused4_program_build
+constexpr int32_t kRaggedMagic = 0x54525247;  // 'TRRG' trex_ragged_plan_build
+constexpr int32_t kNniMagic = 0x54524E4E;     // 'TRNN' trex_nni_plan_build
+constexpr int32_t kAttachMagic = 0x54524154;  // 'TRAT' trex_attach_plan_build
 constexpr size_t kLdsPerCu = 160 * 1024;    // gfx950: LDS bytes of a CU, the most one workgroup can take
 
-// forward-step child descriptor: index bits 0-15, slot 16-23, kind 24-25
+// leaves / internal rows of a tree of n_all nodes
+inline int tree_nl(int n_all) { return (n_all + 1) / 2; }
+inline int tree_ni(int n_all) { return n_all - tree_nl(n_all); }
+
+// forward-step child descriptor: index bits 0-15, slot 16-23, kind 24-25,
+// flags above.  Kinds: a row that still holds the 1e5 init (index 0), a leaf
+// (leaf index), an internal row (row, and the LDS slot its vector is in), a
+// row the lane-per-site program computes inline (its index in the inline list)
+constexpr int kKindSent = 0, kKindLeaf = 1, kKindInt = 2, kKindInline = 3;
+inline int32_t child_desc(int kind, int index, int slot = 0, int32_t flags = 0) {
+  return (index & 0xFFFF) | ((slot & 0xFF) << 16) | (kind << 24) | flags;
+}
+// node id -> leaf or internal-row descriptor (NNI and attach plans)
+inline int32_t node_desc(int node, int nl) {
+  return node < nl ? child_desc(kKindLeaf, node) : child_desc(kKindInt, node - nl);
+}
+inline int desc_index(int32_t d) { return d & 0xFFFF; }
+inline int desc_slot(int32_t d) { return (d >> 16) & 0xFF; }
+inline int desc_kind(int32_t d) { return (d >> 24) & 3; }
+// word 0 of a step: the row it computes, the slot its vector goes to
+inline int32_t step_row(int row, int slot = 0) { return child_desc(0, row, slot); }
 constexpr int32_t kStepAccumulate = 1 << 26;  // adjoint: add into the slot
 // register bypass: this internal child is the previous step's node (its only
 // consumer is this step): forward reads its D from registers, the adjoint
@@ -57,9 +82,49 @@ inline int64_t staged_tree_ints(int ni) {
 //     [n_inline][4] = {row, child desc 0, child desc 1, height}, children first.
 //   child desc: kind << 24 | (sentinel: 0; leaf: leaf index; task row:
 //     row | slot << 16 (kKindInt); inline row: its index (kKindInline))
-constexpr int kKindInline = 3;
 inline int64_t lp_steps_offset(int ni) { return 8 + (((int64_t)ni + 1 + 3) & ~3LL); }
 inline int64_t lp_tree_ints(int ni) { return lp_steps_offset(ni) + 4LL * ni; }
+
+// Where a uniform plan's regions start, in ints from the plan's first:
+// header | fwd steps [B][ni][4] | backtrack entries [B][ni][2] | staged
+// regions [B] | lane-per-site regions [B].  The writer (plan.cpp) and the
+// readers (sankoff.hip) both take their pointers from here.
+struct PlanLayout {
+  int64_t fwd, bt, staged, lanes, total;
+};
+inline PlanLayout plan_layout(int B, int ni) {
+  const int64_t fwd = TREX_PLAN_HEADER_INTS, bt = fwd + (int64_t)B * ni * 4,
+                staged = bt + (int64_t)B * ni * 2, lanes = staged + B * staged_tree_ints(ni);
+  return {fwd, bt, staged, lanes, lanes + B * lp_tree_ints(ni)};
+}
+
+// A ragged plan (trees of different sizes n_all_b and site counts L_b in one
+// launch; one work item = one tree x 64-site tile): header | per-tree records
+// [B][kRaggedMeta] | work item -> tree [items] | fwd steps [steps][4] |
+// backtrack entries [steps][2], steps = sum n_int_b.  The kernels index the
+// plan from its records on (rmeta) by the same sums.
+constexpr int kRaggedMeta = 12;  // ints per tree record, the last two spare
+enum RaggedRecord {
+  kRecStep = 0,  // the tree's first step
+  kRecNInt,
+  kRecNLeaves,
+  kRecL,
+  kRecSite,    // its first site in the packed site arrays
+  kRecItem,    // its first work item
+  kRecLeafLo,  // its offset in the packed leaf bytes (64 bits)
+  kRecLeafHi,
+  kRecRowsLo,  // its offset in the packed DP row-sites (64 bits)
+  kRecRowsHi,
+};
+struct RaggedLayout {
+  int64_t meta, item, fwd, bt, total;
+};
+// a reader that stops at the steps may pass steps = 0
+inline RaggedLayout ragged_layout(int B, int64_t items, int64_t steps) {
+  const int64_t meta = TREX_PLAN_HEADER_INTS, item = meta + (int64_t)B * kRaggedMeta,
+                fwd = item + items, bt = fwd + steps * 4;
+  return {meta, item, fwd, bt, bt + steps * 2};
+}
 
 // Fused Q = 4 program (trex_fused4_program_build, plan.cpp; run by
 // sankoff_fused4.hip): the plan's forward steps decoded once on the host, so
@@ -83,7 +148,6 @@ inline int64_t lp_tree_ints(int ni) { return lp_steps_offset(ni) + 4LL * ni; }
 // kF4LeafInt one leaf and one internal child (kF4Leaf0 tells which: the sum
 // of the two messages commutes); kF4IntInt.  The reverse sweep runs the
 // children in stored order off the flag bits (the dC sums depend on the order).
-constexpr int32_t kF4Magic = 0x54524634;  // 'TRF4'
 constexpr int kF4RecInts = 8;
 constexpr int32_t kF4Leaf0 = 1, kF4Leaf1 = 2;    // child 0 / 1 is a leaf
 constexpr int32_t kF4Prev0 = 4, kF4Prev1 = 8;    // kChildPrev of child 0 / 1
@@ -235,7 +299,6 @@ int bigq_backtrack(const int32_t* bt, const float* cost, const float* dp, int B,
                    int Q, int8_t* anc, void* stream);
 int bigq_ragged_backtrack(const int32_t* rmeta, int B, int64_t items, int64_t steps,
                           const float* cost, const float* dp, int Q, int8_t* anc, void* stream);
-constexpr int kRaggedMeta = 12;  // ints per tree record of a ragged plan (plan.cpp)
 int wide_group(int Q);
 int wide_tiles(int L, int Q);
 size_t wide_lds_bytes(int n_slots, int nl, int ni, int Q);
@@ -257,7 +320,7 @@ struct RaggedParts {
   int stride, items, scale;
 };
 inline RaggedParts ragged_parts(const SankoffCall& c, int scale = 1) {
-  return {c.rmeta + 5, kRaggedMeta, (int)c.items, scale};
+  return {c.rmeta + kRecItem, kRaggedMeta, (int)c.items, scale};
 }
 // fixed-order sum of per-item partials -> c.tree_score [B] (phase & 1),
 // c.d_cost [Q*Q] (phase & 2); part_dc is [Q*Q][B*tiles] (ragged: tiles is

@@ -23,7 +23,7 @@ from __future__ import annotations
 import numpy as np
 
 from ._lib import TREX_FLAG_HARD_ROOT, TREX_PLAN_HEADER_INTS, check, lib, ptr, stream_handle
-from .topology import children_from_adjacency
+from .topology import children_from_adjacency, device_copy
 
 
 def _torch():
@@ -72,12 +72,7 @@ class RaggedTreePlan:
         return cls([children_from_adjacency(a)[0] for a in adjacencies], L_list)
 
     def device(self, device):
-        import torch
-
-        key = str(device)
-        if key not in self._dev:
-            self._dev[key] = torch.from_numpy(self.host).to(device)
-        return self._dev[key]
+        return device_copy(self._dev, self.host, device)
 
     # -- packing helpers (host) -------------------------------------------
     def pack_leaves(self, leaves_list) -> np.ndarray:

@@ -7,6 +7,8 @@ child of node ``j`` (src/trex/utils/types.py:30-35).  Leaves are
 
 from __future__ import annotations
 
+import functools
+
 import numpy as np
 
 from ._lib import TREX_PLAN_HEADER_INTS, check, lib
@@ -213,6 +215,32 @@ def relabel_leaves(children, perm) -> np.ndarray:
     return _renumber(kids, n_all - 1, leaf_id, lambda node: leaf_id.get(node, node))
 
 
+def _build_plan(name: str, what: str, children: np.ndarray, B: int, n_all: int,
+                *info) -> np.ndarray:
+    """trex_<name>_ints, an int32 buffer of that size, trex_<name>_build into
+    it (``info``: the builder's trailing output arrays; ``what``: the plan in
+    words).  TrexError when the builder refuses the trees."""
+    L = lib()
+    n = getattr(L, f"trex_{name}_ints")(B, n_all)
+    if n <= 0:
+        raise ValueError(f"bad {what} shape B={B} n_all={n_all}")
+    buf = np.zeros(n, dtype=np.int32)
+    check(getattr(L, f"trex_{name}_build")(children.ctypes.data, B, n_all, buf.ctypes.data,
+                                           *(a.ctypes.data for a in info)))
+    return buf
+
+
+def device_copy(cache: dict, host: np.ndarray, device):
+    """``host`` as a device tensor, copied once per device (``cache``: the
+    copies made so far, by device)."""
+    import torch
+
+    key = str(device)
+    if key not in cache:
+        cache[key] = torch.from_numpy(host).to(device)
+    return cache[key]
+
+
 class TreePlan:
     """A batch of topologies compiled by the host planner (trex_plan_build)."""
 
@@ -225,14 +253,8 @@ class TreePlan:
         self.B, self.n_all, _ = ch.shape
         self.n_leaves = (self.n_all + 1) // 2
         self.n_int = self.n_all - self.n_leaves
-        L = lib()
-        n = L.trex_plan_ints(self.B, self.n_all)
-        if n <= 0:
-            raise ValueError(f"bad plan shape B={self.B} n_all={self.n_all}")
-        self.host = np.zeros(n, dtype=np.int32)
         info = np.zeros(4, dtype=np.int32)
-        check(L.trex_plan_build(ch.ctypes.data, self.B, self.n_all, self.host.ctypes.data,
-                                info.ctypes.data))
+        self.host = _build_plan("plan", "plan", ch, self.B, self.n_all, info)
         self.children = ch
         # info[0]: stack depth | (lane-program slots + 1) << 16; the C calls
         # take the whole word
@@ -242,62 +264,30 @@ class TreePlan:
         self.backtrack_ok = int(info[1])
         self.n_dag_nodes = int(info[2])
         self.n_unreached = int(info[3])
-        self._dev = {}
-        self._nni_host = None
-        self._nni_dev = {}
-        self._attach_host = None
-        self._attach_dev = {}
+        self._dev = {"plan": {}, "nni": {}, "attach": {}}
 
     # -- NNI plan (trex_nni_plan_build), built on first use ------------------
-    @property
+    @functools.cached_property
     def nni_host(self) -> np.ndarray:
         """The NNI plan (include/trex_hip.h) as int32; TrexError
         (TREX_E_TOPOLOGY) when a tree of the batch is not a proper rooted
         binary tree of at least 3 leaves."""
-        if self._nni_host is None:
-            L = lib()
-            n = L.trex_nni_plan_ints(self.B, self.n_all)
-            if n <= 0:
-                raise ValueError(f"bad NNI plan shape B={self.B} n_all={self.n_all}")
-            buf = np.zeros(n, dtype=np.int32)
-            check(L.trex_nni_plan_build(self.children.ctypes.data, self.B, self.n_all,
-                                        buf.ctypes.data))
-            self._nni_host = buf
-        return self._nni_host
+        return _build_plan("nni_plan", "NNI plan", self.children, self.B, self.n_all)
 
     def nni_device(self, device):
         """The NNI plan as an int32 device tensor (cached per device)."""
-        import torch
-
-        key = str(device)
-        if key not in self._nni_dev:
-            self._nni_dev[key] = torch.from_numpy(self.nni_host).to(device)
-        return self._nni_dev[key]
+        return device_copy(self._dev["nni"], self.nni_host, device)
 
     # -- attach plan (trex_attach_plan_build), built on first use -------------
-    @property
+    @functools.cached_property
     def attach_host(self) -> np.ndarray:
         """The attach plan (include/trex_hip.h) as int32; TrexError as for
         ``nni_host``."""
-        if self._attach_host is None:
-            L = lib()
-            n = L.trex_attach_plan_ints(self.B, self.n_all)
-            if n <= 0:
-                raise ValueError(f"bad attach plan shape B={self.B} n_all={self.n_all}")
-            buf = np.zeros(n, dtype=np.int32)
-            check(L.trex_attach_plan_build(self.children.ctypes.data, self.B, self.n_all,
-                                           buf.ctypes.data))
-            self._attach_host = buf
-        return self._attach_host
+        return _build_plan("attach_plan", "attach plan", self.children, self.B, self.n_all)
 
     def attach_device(self, device):
         """The attach plan as an int32 device tensor (cached per device)."""
-        import torch
-
-        key = str(device)
-        if key not in self._attach_dev:
-            self._attach_dev[key] = torch.from_numpy(self.attach_host).to(device)
-        return self._attach_dev[key]
+        return device_copy(self._dev["attach"], self.attach_host, device)
 
     @property
     def nni_table(self) -> np.ndarray:
@@ -320,12 +310,7 @@ class TreePlan:
 
     def device(self, device):
         """The plan as an int32 device tensor (cached per device)."""
-        import torch
-
-        key = str(device)
-        if key not in self._dev:
-            self._dev[key] = torch.from_numpy(self.host).to(device)
-        return self._dev[key]
+        return device_copy(self._dev["plan"], self.host, device)
 
     @property
     def fwd_steps(self) -> np.ndarray:
