@@ -387,6 +387,7 @@ Route route(const SankoffCall& c, int slot_word, bool has_prog, int64_t workspac
   // takes the calls in its scope; same partials, same reduce
   const bool fused4 = has_prog && c.phase == 3 && c.Q == 4 && c.soft && !c.site_score &&
                       !c.marg && !c.anc && (c.L & 3) == 0 && c.nl <= kPrefetchRows &&
+                      f4_lds_bytes(c.n_slots, c.nl) <= 65536 &&  // else the one-wave kernel
                       env_switch("TREX_FUSED4") != 0;
   r.family = fused4 ? Family::kFused4 : Family::kQ4;
   return r;
@@ -397,7 +398,9 @@ Route route(const SankoffCall& c, int slot_word, bool has_prog, int64_t workspac
 int q4_run(const char* fn, const SankoffCall& c, const int32_t* prog = nullptr) {
   if ((int64_t)c.ni * c.L * c.Q * 4 > 0x7FFFFFF0LL)
     return set_error(TREX_E_UNSUPPORTED, "%s: one tree's DP table exceeds 2 GiB", fn);
-  const size_t lds = lds_bytes(c.n_slots, c.nl, c.Q, c.phase);
+  // the fused Q = 4 kernel's workgroups are kF4Waves waves on shared tables
+  const size_t lds =
+      prog ? f4_lds_bytes(c.n_slots, c.nl) : lds_bytes(c.n_slots, c.nl, c.Q, c.phase);
   if (lds > 65536) return set_error(TREX_E_UNSUPPORTED, "%s: LDS stack too deep", fn);
   if ((int64_t)c.B * q4_tiles(c.L) > 0x7FFFFFFF)
     return set_error(TREX_E_ARG, "%s: grid too large", fn);

@@ -1,14 +1,20 @@
 // Fused forward + adjoint for Q = 4 softmin on a predecoded program
 // (trex_fused4_program_build, plan.cpp; record layout: trex_common.h).
 //
-// The same work item, LDS map, tables, slot stack, XCD item mapping, cache
-// policies, ring depth and fp64 partials as sankoff_kernel<4, true, 3>
-// (sankoff_q4_dev.h), and the same arithmetic in the same order, so dp,
-// tree_score and d_cost are bitwise the generic kernel's.  What differs is the
-// step interpreter: the generic body decodes every step's descriptors on the
-// scalar pipe, in both sweeps, for every one of a tree's tiles; here the
-// planner has done that once and the loops switch on a step class and read
-// operands (LDS byte offsets, re-read rows) from a 32-byte record.
+// The same work item, tables, slot stack, cache policies, ring depth and fp64
+// partials as sankoff_kernel<4, true, 3> (sankoff_q4_dev.h), and the same
+// arithmetic in the same order, so dp, tree_score and d_cost are bitwise the
+// generic kernel's.  What differs is the step interpreter: the generic body
+// decodes every step's descriptors on the scalar pipe, in both sweeps, for
+// every one of a tree's tiles; here the planner has done that once and the
+// loops switch on a step class and read operands (LDS byte offsets, re-read
+// rows) from a 32-byte record.
+//
+// Workgroups are kF4Waves waves, one item each, on one copy of the leaf and
+// pair tables, built once per workgroup: LDS is [tables][wave 0: slot stack,
+// leaf tile][wave 1 ...] (sankoff_q4_dev.h), the records' offsets relative to a
+// wave's corner.  Only the prologue has barriers; a wave without an item (a
+// short last workgroup) passes them and leaves.
 //
 // Scope (route, sankoff.hip, checks it): uniform batch, tau > 0, leaf
 // tile prefetchable (L % 4 == 0, <= 64 leaves), no site scores, marginals or
@@ -34,38 +40,37 @@ __device__ __forceinline__ F4Rec load_rec(cptr<int> prog, int k) {
   return F4Rec{p[0], p[1], p[2], p[3], p[4], p[5], p[6]};
 }
 
+// wave: the wave's index in its workgroup; item: its item (-1: none)
 template <bool SYM>
-__device__ __forceinline__ void fused4_body(const KArgs& A, const int* prog_, float* lds) {
+__device__ __forceinline__ void fused4_body(const KArgs& A, const int* prog_, float* lds, int wave,
+                                            int item) {
   constexpr int Q = 4;
   constexpr int MODE = kSoftK;
-  const int lane = threadIdx.x;
+  const int tid = threadIdx.x;
+  const int lane = tid & (kWave - 1);
   const int L = A.L;
   const float a = A.a, bcoef = A.bcoef;
   const int nb = A.nblocks;
-  const int per = (nb + 7) / 8;
-  const int xcd = blockIdx.x & 7;
-  const int item_end = min(nb, (xcd + 1) * per);
-  const int item = xcd * per + (blockIdx.x >> 3);
-  if (item >= item_end) return;
 
   Coef<Q> cf;
   load_coef<Q, MODE>(A.cost, a, cf);
 
-  // LDS map of the fused generic kernel (sankoff_q4_dev.h)
+  // the workgroup's tables, then this wave's slot stack and leaf tile
   float* tab = lds;
-  float* slots = lds + tab_floats(3);
+  float* slots = f4_wave_lds(lds, wave, A.n_slots, A.nl);
   float* tm = tab + kLeafTabFloats;
   float* tu = tab + kLeafTabFloats + kPairFloats;
   float* tr = tab + kLeafTabFloats + 2 * kPairFloats;
   int8_t* lleaf = reinterpret_cast<int8_t*>(slots + (size_t)max(A.n_slots, 1) * Q * kWave);
 
-  // ---- once per wave: leaf tables, then pair tables (as sankoff_body) ----
+  // ---- once per workgroup, one thread per entry (all of wave 0): leaf
+  // tables, then pair tables (as sankoff_body) ----
   {
     float cmn, cmx;
     cost_range<Q>(A.cost, cmn, cmx);
     const float range = cmx - cmn;
     const bool lfast = (kSentinel - range) * a >= 64.0f;
-    if (lane <= Q) {
+    if (tid <= Q) {
       const cptr<float> cost = as_const(A.cost);
       float d1[Q], m1[Q], g1[Q], w1[Q][Q], gc1[Q];
 #pragma unroll
@@ -98,8 +103,8 @@ __device__ __forceinline__ void fused4_body(const KArgs& A, const int* prog_, fl
       }
     }
   }
-  __syncthreads();  // T is written by lanes <= Q
-  if (lane < (Q + 1) * (Q + 1)) {
+  __syncthreads();  // T is written by threads <= Q
+  if (tid < (Q + 1) * (Q + 1)) {
     const int c0 = lane / (Q + 1), c1 = lane - c0 * (Q + 1);
     float t0[Q], t1[Q], d1[Q], m1[Q], u[Q], rs[Q];
     lds_vec_get<Q>(tab + c0 * Q, t0);
@@ -111,6 +116,10 @@ __device__ __forceinline__ void fused4_body(const KArgs& A, const int* prog_, fl
     softk_weights<Q, SYM>(cf, a, d1, u, rs);
     lds_vec_put<Q>(tu + lane * Q, u);
     lds_vec_put<Q>(tr + lane * Q, rs);
+  }
+  if (item < 0) {
+    __syncthreads();  // the one below
+    return;
   }
 
   // ---- this item ----
@@ -132,7 +141,7 @@ __device__ __forceinline__ void fused4_body(const KArgs& A, const int* prog_, fl
 #pragma unroll
     for (int r = 0; r < kPrefetchRows / 4; ++r)
       pre[r] = __builtin_amdgcn_raw_buffer_load_b32(rl, pf_voff, 4 * r * L + tile * kWave, kAuxLeaf);
-    __syncthreads();  // the tables are written by a few lanes, read by all
+    __syncthreads();  // the tables are written by a few threads, read by all
     uint32_t* dst = reinterpret_cast<uint32_t*>(lleaf);
 #pragma unroll
     for (int r = 0; r < kPrefetchRows / 4; ++r) {
@@ -385,19 +394,37 @@ __device__ __forceinline__ void fused4_body(const KArgs& A, const int* prog_, fl
   if ((lane & 3) == 0) A.part_dc[(size_t)(lane >> 2) * nb + item] = v;
 }
 
-__global__ __launch_bounds__(kWave)
+// Workgroups of XCD x (blockIdx % 8) take a contiguous range of the
+// ceil(items / kF4Waves) item groups, wave w of a workgroup item
+// kF4Waves * group + w: the waves of a workgroup, and of an XCD, work on
+// adjacent tiles.  The items themselves (part_tree / part_dc) are numbered as
+// in every Q <= 4 kernel.
+__host__ __device__ inline int f4_groups(int items) { return (items + kF4Waves - 1) / kF4Waves; }
+
+__global__ __launch_bounds__(kF4Waves * kWave)
 __attribute__((amdgpu_waves_per_eu(kFusedWpe, kFusedWpeMax)))
 void sankoff_fused4_kernel(KArgs A, const int* prog) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int groups = f4_groups(A.nblocks);
+  const int per = (groups + 7) / 8;
+  const int xcd = blockIdx.x & 7;
+  const int group = xcd * per + (blockIdx.x >> 3);
+  if (group >= min(groups, (xcd + 1) * per)) return;  // the whole workgroup
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
+  int item = group * kF4Waves + wave;
+  if (item >= A.nblocks) item = -1;  // still passes every barrier
   float cmin, cmax;
   cost_range<4>(A.cost, cmin, cmax);
   if (use_ktrick(cmin, cmax, A.a)) {
     if (cost_symmetric<4>(A.cost))
-      fused4_body<true>(A, prog, lds);
+      fused4_body<true>(A, prog, lds, wave, item);
     else
-      fused4_body<false>(A, prog, lds);
+      fused4_body<false>(A, prog, lds, wave, item);
   } else {
-    sankoff_body<4, kSoftDirect, 3, false>(A, lds);
+    // the generic body per wave, on the same map: every wave writes the shared
+    // tables (the same values) and keeps its own slot stack and leaf tile
+    sankoff_body<4, kSoftDirect, 3, false, false, true>(
+        A, lds, item, f4_wave_lds(lds, wave, A.n_slots, A.nl));
   }
 }
 
@@ -407,8 +434,9 @@ int g_fused4_launches = 0;  // tests: which kernel took a call
 
 int fused4_run(const char* fn, const SankoffCall& c, const int32_t* prog, size_t lds) {
   const KArgs A = q4_args(c);
-  const int grid = (A.nblocks + 7) / 8 * 8;
-  hipLaunchKernelGGL(sankoff_fused4_kernel, dim3(grid), dim3(kWave), lds, (hipStream_t)c.stream, A,
+  const int grid = (f4_groups(A.nblocks) + 7) / 8 * 8;
+  hipLaunchKernelGGL(sankoff_fused4_kernel, dim3(grid), dim3(kF4Waves * kWave), lds,
+                     (hipStream_t)c.stream, A,
                      reinterpret_cast<const int*>(prog + TREX_PLAN_HEADER_INTS));
   ++g_fused4_launches;
   return hip_check(fn);

@@ -465,6 +465,21 @@ constexpr int kPairFwd = 28;      // forward-only: TM at [28, 128)
 constexpr int tab_floats(int phase) {
   return kLeafTabFloats + ((kPairTables && phase != 1) ? 3 * kPairFloats : 0);
 }
+// The fused Q = 4 kernel (sankoff_fused4.hip) runs workgroups of kF4Waves
+// waves, one item each, on one copy of the tables above: [tab_floats(3)], then
+// every wave's own slot stack and leaf tile (f4_wave_lds).  1 712 B of tables
+// per workgroup instead of per wave; at C4 (3 slots, 32 leaves) a workgroup is
+// 22 192 B, five per CU as the registers allow.
+constexpr int kF4Waves = 4;
+__host__ __device__ inline size_t f4_wave_bytes(int n_slots, int nl) {
+  return (size_t)(n_slots > 1 ? n_slots : 1) * 4 * kWave * 4 + (size_t)nl * kWave;
+}
+__device__ inline float* f4_wave_lds(float* lds, int wave, int n_slots, int nl) {
+  return lds + tab_floats(3) + wave * (f4_wave_bytes(n_slots, nl) / 4);
+}
+inline size_t f4_lds_bytes(int n_slots, int nl) {
+  return (size_t)tab_floats(3) * 4 + kF4Waves * f4_wave_bytes(n_slots, nl);
+}
 // Sites per lane.  Only one was ever built (two doubled the adjoint's VGPRs
 // and were slower at every grid measured) and the code
 // carries no second one.  The one-trip `for (s < kSites)` loops that remain in
@@ -488,12 +503,19 @@ constexpr int kPrefetchRows = 64;  // leaf tiles of <= 64 leaves are prefetched
 // in LDS, no adjoint re-read, one wave per SIMD -- measured 2.3x slower on the
 // C4 shard and on par for C2; removed in round 3 with the other A/B-only
 // variants)
-template <int Q, int MODE, int PHASE, bool RAGGED, bool SYM = false>
-__device__ __forceinline__ void sankoff_body(const KArgs& A, float* lds) {
+//
+// MULTI (sankoff_fused4.hip, not persistent): the caller is one wave of a
+// multi-wave workgroup and passes its item (-1: none) and its own slot stack
+// and leaf tile (wave_lds); the tables at lds are the workgroup's, written by
+// every wave with the same values.  The barriers below are then the
+// workgroup's: a wave without an item passes them and leaves.
+template <int Q, int MODE, int PHASE, bool RAGGED, bool SYM = false, bool MULTI = false>
+__device__ __forceinline__ void sankoff_body(const KArgs& A, float* lds, int wave_item = -1,
+                                             float* wave_lds = nullptr) {
   constexpr bool SOFT = MODE != kHard;
   constexpr bool FWD = (PHASE & 1) != 0;
   constexpr bool BWD = (PHASE & 2) != 0;
-  const int lane = threadIdx.x;
+  const int lane = MULTI ? threadIdx.x & (kWave - 1) : threadIdx.x;
   const int L = A.L;
   const float a = A.a, bcoef = A.bcoef;
   const int nb = A.nblocks;
@@ -502,13 +524,23 @@ __device__ __forceinline__ void sankoff_body(const KArgs& A, float* lds) {
   const int stride = gridDim.x >> 3;
   const int item_end = min(nb, (xcd + 1) * per);
   int item = xcd * per + (blockIdx.x >> 3);
-  if (item >= item_end) return;
+  if constexpr (MULTI) {
+    static_assert(PHASE != 1, "the persistent loop walks one-wave grids");
+    item = wave_item;
+    if (item < 0) {
+      if constexpr (kPairTables) __syncthreads();
+      __syncthreads();
+      return;
+    }
+  } else {
+    if (item >= item_end) return;
+  }
 
   Coef<Q> cf;
   load_coef<Q, MODE>(A.cost, a, cf);
 
   float* tab = lds;
-  float* slots = lds + tab_floats(PHASE);
+  float* slots = MULTI ? wave_lds : lds + tab_floats(PHASE);
   // pair tables (see the LDS map)
   float* tm = tab + (PHASE == 1 ? kPairFwd : kLeafTabFloats);
   float* tu = tab + kLeafTabFloats + kPairFloats;
