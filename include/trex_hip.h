@@ -379,7 +379,9 @@ int trex_tree_mf_rows_x3_codes(const float* M, const float* S, int N, int64_t K,
  * (no clipping; dtheta may be NULL; state non-NULL: bias corrections from it,
  * count ignored).  tree.py:133-160 / 50-107 and optax adam.  M16 (optional):
  * M also written pre-split for trex_tree_mf_rows_x3p (below), ldm16 >= N
- * f32-equivalent columns per row, zero past N. */
+ * f32-equivalent columns per row (ldm16 % 4 == 0), zero past N.  The call
+ * itself writes those zeros: every column [0, ldm16) of each of the N rows of
+ * M16 is written, so the caller need not clear the buffer. */
 int trex_tree_surrogate_constraint(const float* A, const float* G, int N, float scale,
                                    float grad_scale, const void* state, float* loss, float* dA,
                                    float* M, float max_abs_m, void* M16, int ldm16,
@@ -401,7 +403,12 @@ int trex_tree_update_tree_bwd_adam(const float* A, const float* dA, const float*
  * (M16 rows ldm apart, ldm % 32 == 0, zero past N; codes optional);
  * trex_adam_seq_update_step_x3p == trex_adam_seq_update_step[_dev] (state
  * NULL: count / temperatures from the arguments) writing the next S rows
- * pre-split into s16_next (Q = 4, 16-B aligned). */
+ * pre-split into s16_next (Q = 4, 16-B aligned).
+ * Padding is the kernels' to write, never the caller's: trex_tree_split_x3
+ * writes all ldo columns of each of the `rows` rows of `out` (zero groups
+ * past cols), as trex_tree_surrogate_constraint does for M16; the x3p GEMMs
+ * read M16 columns [0, ldm) of rows [row0, row0 + nrows) and S16 columns
+ * [0, K) of rows [0, N) and nothing else that reaches a result. */
 int trex_tree_split_x3(const float* X, int rows, int cols, int ldx, float max_abs, void* out,
                        int ldo, void* stream);
 int trex_tree_gram_skip_x3p(const void* S16, int N, int64_t K, int skip_rows, float max_abs,

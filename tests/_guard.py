@@ -24,6 +24,15 @@ the size the matching ``*_workspace_bytes`` function returns, zeroed with
 trex_workspace_init where the header asks for that and prefilled like an
 output where it does not.
 
+An output (or in/out table) may have a **kept region** (``keep=``: a boolean
+mask of its entries): entries the header says the call leaves alone --
+trex_tree_gram_skip's cached block, trex_datagen_nk_tree's root row, padding
+that is the caller's to zero.  It is prefilled like any output (``fill=``: the
+caller's bytes there instead, e.g. the zeros a header asks for); after the
+call every kept byte still holds what it held before (a write into the
+region is flagged with its entries), and R1 == R2 == R0 is asked outside it
+only, where a never-written entry shows as ever.
+
 R1 and R2 drive the C ABI directly (one thin wrapper per entry point below,
 argument lists as in trex_amd/sankoff.py and trex_amd/ragged.py), because
 several engine methods allocate their own outputs.
@@ -48,6 +57,12 @@ def _bytes_of(x):
     else:
         t = torch.from_numpy(np.ascontiguousarray(x))
     return t.reshape(-1).view(torch.uint8).clone()
+
+
+def _entry_bytes(view):
+    """(numel, itemsize) uint8 CPU tensor: the bytes of every entry."""
+    t = view.detach().cpu().contiguous()
+    return t.reshape(-1).view(torch.uint8).reshape(t.numel(), t.element_size())
 
 
 class Guarded:
@@ -122,6 +137,7 @@ class Run:
         self.r = r
         self.p = PROTOCOL[r]
         self.inputs, self.outputs, self.scratch = {}, {}, {}
+        self.keep = {}  # output name -> (bool mask of kept entries, their bytes before the call)
 
     def _add(self, table, name, handle):
         assert not any(name in t for t in (self.inputs, self.outputs, self.scratch)), name
@@ -137,13 +153,24 @@ class Run:
         self._add(self.inputs, name, h)
         return v
 
-    def output(self, name, shape, dtype):
+    def _keep(self, name, view, keep, fill=None):
+        """Register the kept region of output ``name`` (see the module
+        docstring); fill: a value written to the kept entries first."""
+        if keep is None:
+            return
+        mask = torch.as_tensor(np.asarray(keep, dtype=bool)).reshape(tuple(view.shape))
+        if fill is not None:
+            view.masked_fill_(mask.to(view.device), fill)
+        self.keep[name] = (mask, _entry_bytes(view)[mask.reshape(-1)].clone())
+
+    def output(self, name, shape, dtype, keep=None, fill=None):
         v, h = guarded(shape, dtype, self.device, payload=self.p["prefill"],
                        guard_byte=self.p["out_guard"])
         self._add(self.outputs, name, h)
+        self._keep(name, v, keep, fill)
         return v
 
-    def inout(self, name, array):
+    def inout(self, name, array, keep=None):
         """An in/out table: the caller's bytes between output guards; what the
         call leaves of them is compared between the runs like an output."""
         dtype = array.dtype if isinstance(array, torch.Tensor) else torch.from_numpy(
@@ -151,6 +178,7 @@ class Run:
         v, h = guarded(tuple(array.shape), dtype, self.device, payload=array,
                        guard_byte=self.p["out_guard"])
         self._add(self.outputs, name, h)
+        self._keep(name, v, keep)
         return v
 
     def workspace(self, nbytes, init=False, name="workspace"):
@@ -175,6 +203,15 @@ class Run:
                 h.check(f"R{self.r} {kind} {name}")
         for name, h in self.inputs.items():
             h.unchanged(f"R{self.r} input {name}")
+        for name, (mask, before) in self.keep.items():
+            now = _entry_bytes(self.outputs[name].view)[mask.reshape(-1)]
+            bad = (now != before).any(dim=1).nonzero().reshape(-1)
+            if bad.numel():
+                idx = mask.reshape(-1).nonzero().reshape(-1)[bad]
+                raise AssertionError(
+                    f"R{self.r} output {name}: kept region written: {bad.numel()} of "
+                    f"{int(mask.sum())} kept entries changed, first at flat index {int(idx[0])}, "
+                    f"last at {int(idx[-1])} of {mask.numel()}")
         return {name: h.view.cpu().clone() for name, h in self.outputs.items()}
 
 
@@ -204,17 +241,26 @@ def protocol(device, r0, call):
     if torch.device(device).type == "cuda":
         torch.cuda.synchronize(device)
     ref = {k: v.detach().cpu().clone() for k, v in ref.items() if v is not None}
-    outs = {}
+    outs, keep = {}, {}
     for r in (1, 2):
         run = Run(device, r)
         call(run)
         outs[r] = run.finish()
+        keep[r] = {k: m for k, (m, _) in run.keep.items()}
     assert set(outs[1]) == set(outs[2]) and set(ref) <= set(outs[1]), (sorted(ref), sorted(outs[1]))
+    assert set(keep[1]) == set(keep[2]) and all(torch.equal(keep[1][k], keep[2][k])
+                                                for k in keep[1]), "kept regions differ"
+
+    def outside(k, t):
+        """t with its kept entries (checked by finish) zeroed."""
+        return t.masked_fill(keep[1][k], 0) if k in keep[1] else t
+
     for k in outs[1]:
-        assert_bitwise(outs[1][k], outs[2][k], f"{k}: R1 vs R2 (an entry never written, or a "
-                       "read outside an input)")
+        assert_bitwise(outside(k, outs[1][k]), outside(k, outs[2][k]),
+                       f"{k}: R1 vs R2 (an entry never written, or a read outside an input)")
     for k in ref:
-        assert_bitwise(outs[1][k], ref[k].reshape(outs[1][k].shape), f"{k}: R1 vs R0")
+        assert_bitwise(outside(k, outs[1][k]), outside(k, ref[k].reshape(outs[1][k].shape)),
+                       f"{k}: R1 vs R0")
     return outs[1]
 
 

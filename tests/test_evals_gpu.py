@@ -71,6 +71,35 @@ def test_ancestor_optimizer_matches_oracle_loop(device, name, L):
         assert np.all(err <= slack), (step, float((err - slack).max()))
 
 
+def test_ancestor_optimizer_keeps_x3_off_leaves_beyond_its_contract(device):
+    """The f16x3 GEMMs' contract is |S| <= 1 (include/trex_hip.h: a larger
+    value overflows f16).  Leaf rows are the caller's data: one-hot x integer
+    weights 1..8 at today's x3 shape (K = 256) must run the f32 GEMMs -- at
+    max_abs = 1 the split scale is 2^14, so an entry >= 4 is inf in f16 and
+    the loss is non-finite.  Same bars as the test above."""
+    nl, L, Q, lr = 8, 64, 4, 0.05
+    leaves, S0, anc, A = _case(nl, L, Q, seed=L)
+    assert E.AncestorOptimizer(S0, nl, A, anc, "adam", lr, device=device).x3 is True
+    S0 = S0.copy()
+    S0[:nl] *= np.arange(1, nl + 1, dtype=np.float32)[:, None, None]
+    opt = E.AncestorOptimizer(S0, nl, A, anc, "adam", lr, device=device)
+    for step in range(1, 3):
+        p = opt.params["ancestors"].detach().cpu().numpy().astype(np.float64)
+        loss = float(opt.step())
+        torch.cuda.synchronize()
+        g = opt.grads["ancestors"].detach().cpu().numpy().astype(np.float64)
+        rl, rg = T.fixed_tree_loss_grad(p, S0, nl, A)
+        assert np.isfinite(loss), (step, loss)
+        np.testing.assert_allclose(loss, rl, rtol=1e-5)
+        S = np.array(S0, dtype=np.float64)
+        P = np.exp(p - p.max(-1, keepdims=True))
+        P /= P.sum(-1, keepdims=True)
+        S[nl:] = P
+        bS, _ = surrogate_grad_bounds(S, A, 1e-5)
+        assert_bound_close(g, rg, softmax_vjp_bound(P, bS[nl:]), what=f"grad step {step}")
+    assert opt.x3 is False
+
+
 def test_optimizer_without_clipping_and_unknown_name(device):
     params = {"x": torch.ones(10, device=device)}
     opt = E.create_optimizer("sgd", 0.1, params, use_gradient_clipping=False)

@@ -136,3 +136,80 @@ def test_run_names_are_unique():
     run.input("x", _x())
     with pytest.raises(AssertionError):
         run.output("x", (N,), torch.float32)
+
+
+# ---------------------------------------------------------------------------
+# kept regions (trex_tree_gram_skip's cached block, the root row of
+# trex_datagen_nk_tree's seqs, padding that is the caller's to zero)
+# ---------------------------------------------------------------------------
+KEEP = np.zeros(N, bool)
+KEEP[:8] = True  # the call leaves out[0..8) alone
+
+
+def _kept(run, x, upto=N):
+    """out[i] = 2 x[i] + 1 for 8 <= i < upto."""
+    xi = run.input("x", x)
+    out = run.output("out", (N,), torch.float32, keep=KEEP)
+    out[8:upto].copy_(2.0 * xi[8:upto].to(torch.float32) + 1.0)
+    return xi, out
+
+
+def test_kept_region_holds_each_runs_prefill_and_is_not_compared():
+    """R1's kept bytes are 0x00 and R2's 0xFF -- they differ, and R0's hold
+    whatever the method left there: none of it is compared."""
+    out = protocol(CPU, lambda: {"out": _r0()["out"] + torch.from_numpy(KEEP * 9.0).float()},
+                   lambda run: _kept(run, _x()))
+    assert bool((out["out"][:8] == 0).all())
+    assert_bitwise(out["out"][8:], _r0()["out"][8:], "out")
+
+
+def test_write_into_the_kept_region_is_flagged():
+    def call(run):
+        _, out = _kept(run, _x())
+        out[7] = 1.0  # the same value in both runs: R1 == R2 alone would pass
+    with pytest.raises(AssertionError, match=rf"R1 output out: kept region written: 1 of 8 kept "
+                                             rf"entries changed, first at flat index 7, last at 7 "
+                                             rf"of {N}"):
+        protocol(CPU, _r0, call)
+
+
+def test_entry_outside_the_kept_region_left_unwritten_is_flagged():
+    with pytest.raises(AssertionError, match=rf"out: R1 vs R2.*1 of {N} entries differ, first at "
+                                             rf"flat index {N - 1} "):
+        protocol(CPU, _r0, lambda run: _kept(run, _x(), upto=N - 1))
+
+
+def test_kept_padding_prefilled_by_the_caller_must_stay_as_filled():
+    """fill=: the kept entries hold the caller's value (the zeros a header
+    asks the caller for) in both runs; a call that relies on them may read
+    them, and one that writes them is flagged."""
+    def call(run, spoil):
+        xi = run.input("x", _x())
+        out = run.output("out", (N,), torch.float32, keep=KEEP, fill=0.0)
+        assert bool((out[:8] == 0).all())
+        out[8:].copy_(2.0 * xi[8:].to(torch.float32) + 1.0 + out[:8].sum())
+        if spoil:
+            out[0] = 2.0
+    protocol(CPU, _r0, lambda run: call(run, False))
+    with pytest.raises(AssertionError, match="kept region written: 1 of 8"):
+        protocol(CPU, _r0, lambda run: call(run, True))
+
+
+def test_in_out_table_with_a_kept_row():
+    """trex_datagen_nk_tree's seqs: the root row is the caller's and stays."""
+    t0 = np.arange(12, dtype=np.int8).reshape(3, 4)
+    keep = np.zeros((3, 4), bool)
+    keep[2] = True
+
+    def call(run, spoil):
+        t = run.inout("t", t0, keep=keep)
+        t[:2] = 5
+        if spoil:
+            t[2, 1] = t0[2, 1] + 1
+
+    want = torch.from_numpy(t0.copy())
+    want[:2] = 5
+    protocol(CPU, lambda: {"t": want}, lambda run: call(run, False))
+    with pytest.raises(AssertionError, match=r"output t: kept region written: 1 of 4 kept entries "
+                                             r"changed, first at flat index 9, last at 9 of 12"):
+        protocol(CPU, lambda: {"t": want}, lambda run: call(run, True))

@@ -232,6 +232,30 @@ def test_tree_optimizer_x3_needs_aligned_rows_and_says_so(device):
     assert opt.gemm == "f32"
 
 
+def test_tree_optimizer_x3_needs_leaves_inside_its_contract_and_says_so(device):
+    """The x3 GEMMs' contract is |S| <= 1 (include/trex_hip.h: a larger value
+    overflows f16).  Leaf rows of one-hot x integer weights 1..8 break it: the
+    optimiser warns and runs the f32 GEMMs; one step's loss, dA and the
+    ancestor rows of dS against the fp64 oracle at this file's bars."""
+    nl, L, Q, Tt = 16, 52, 4, 0.8
+    params, noise, seqs = _tree_case(nl, L, Q, 17)
+    seqs[:nl] *= (1 + np.arange(nl) % 8).astype(np.float32)[:, None, None]
+    with pytest.warns(RuntimeWarning, match=r"\|S\| <= 1"):
+        opt = G.TreeOptimizer(_t(seqs, device), {k: _t(v, device) for k, v in params.items()},
+                              lr=0.01, gemm="x3")
+    assert opt.gemm == "f32"
+    loss = float(opt.step(Tt, _t(noise, device)))
+    S = T.update_seq(params["ancestors"].astype(np.float64), seqs, Tt)
+    A = T.update_tree(params["tree_params"].astype(np.float64), noise, 1.0)
+    val, rdS, rdA = T.compute_surrogate_cost_grads(S, A)
+    cg = Tt * T.enforce_graph_constraints_grad(A, 10.0)
+    assert np.isfinite(loss)
+    np.testing.assert_allclose(loss, val + Tt * T.enforce_graph_constraints(A, 10.0), rtol=RTOL)
+    bS, bA = surrogate_grad_bounds(S, A, RTOL, constraint_grad=cg)
+    assert_bound_close(_n(opt.dA), rdA + cg, bA, what="dA")
+    assert_bound_close(_n(opt.dS[nl:]), rdS[nl:], bS[nl:], what="dS")
+
+
 @pytest.fixture(params=["5", "3", "6"])
 def gram_version(request, monkeypatch):
     """Every Gram / MF kernel version: v5 (one wave per SIMD; the f32 default),

@@ -114,6 +114,12 @@ class AncestorOptimizer:
         # f16x3 split GEMMs when the shapes allow (|S| <= 1; M has softmax-free
         # rows here, so its bound is the adjacency's row + column sums)
         self.x3 = self.K % 16 == 0
+        # ... and the x3 contract |S| <= 1 holds for the ancestor rows
+        # (softmaxes) only: the leaf rows are the caller's data, checked once
+        # here (they never change; one sync at construction, none per step).
+        # Larger leaves would overflow the f16 pieces: f32 GEMMs for those
+        if self.x3 and self.n_leaf > 0:
+            self.x3 = bool(self.S[: self.n_leaf].abs().max().item() <= 1.0)
         A_host = np.asarray(adj_matrix, dtype=np.float64)
         self.m_bound = float(np.abs(A_host).sum(0).max() + np.abs(A_host).sum(1).max()
                              + 2.0 * np.abs(A_host).max()) + 1.0

@@ -498,6 +498,17 @@ class TreeOptimizer:
                           "GEMMs need 16-B aligned rows, running the f32 MFMA GEMMs instead",
                           RuntimeWarning, stacklevel=2)
             self.gemm = "f32"
+        # the x3 contract is |S| <= 1: the ancestor rows are softmaxes, the
+        # leaf rows are the caller's data and never change, so one check here
+        # (a sync at construction, none per step) covers every step
+        if self.gemm == "x3" and not bool(self.S[: self.n_leaf].abs().max().item() <= 1.0):
+            import warnings
+
+            warnings.warn("TreeOptimizer: the leaf rows of `sequences` exceed |S| <= 1, the "
+                          "f16x3 GEMMs' operand bound (a larger value overflows their f16 "
+                          "pieces); running the f32 MFMA GEMMs instead",
+                          RuntimeWarning, stacklevel=2)
+            self.gemm = "f32"
         # the leaf x leaf block of G = S S^T is constant (leaf rows are data):
         # computed once here (all-reduced once under site sharding), skipped
         # by every step's Gram.  Rows [g_row0, N) are recomputed each step;
