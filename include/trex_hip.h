@@ -691,6 +691,57 @@ int trex_sankoff_attach_w(const int32_t* attach_plan, const int8_t* leaves, cons
                           const float* weights, float* attach_score, void* workspace,
                           int64_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------
+ * State-set leaves (ambiguity codes, gaps, missing data): a second leaf
+ * encoding for scoring and search.  A leaf's cell is an int32 bit mask, bit j
+ * set = state j is allowed at that site; its inside row is D[j] = 0 where bit
+ * j is set and 1e5 elsewhere.  Mask 1 << c is code c; mask 0 is code -1 (all
+ * 1e5, trex's dropped scatter); (1 << Q) - 1 is missing data (all 0).  Bits
+ * at or above Q are ignored; mask values are never read on the host.
+ * leaf_sets int32 [B][n_leaves][L], sub_sets int32 [B][L], contiguous.
+ * Messages, (+), outside rows, move and attachment scores, the fp64
+ * fixed-order site sums and the site weights are those documented above for
+ * leaf codes; at tau = 0 a site's score is the minimum of the code-path site
+ * scores over all ways of choosing one allowed state per leaf.  Q <= 20,
+ * larger Q returns TREX_E_UNSUPPORTED; B, L, n_all limits and the tau check
+ * are those of trex_sankoff_outside.  Only proper rooted binary trees (the
+ * plan builders refuse anything else with TREX_E_TOPOLOGY).  No adjoint.
+ * Added without a version bump (trex_version() stays 10).
+ *
+ * trex_sankoff_sets_fwd: the forward pass on the plan of
+ *   trex_attach_plan_build (its records in ascending row order are a
+ *   post-order).  dp fp32 [B][n_int][L][Q] (required), in the layout
+ *   trex_sankoff_fwd writes for Q <= 20: trex_sankoff_backtrack and the
+ *   passes below read it as they read that table.  site_score fp32 [B][L]
+ *   (optional) = (+) D_root, or min D_root with TREX_FLAG_HARD_ROOT; any
+ *   other flag is TREX_E_ARG.  tree_score fp32 [B] (required): the site
+ *   scores summed in fp64 in a fixed order (wave butterfly, then the tiles in
+ *   order), rounded once; no atomics, repeated calls are bitwise equal.
+ *   workspace >= trex_sets_fwd_workspace_bytes bytes, no initialisation.
+ * trex_sankoff_sets_outside / _nni_w / _attach_w: trex_sankoff_outside /
+ *   _nni_w / _attach_w with the leaf rows read from masks; dp is the table of
+ *   trex_sankoff_sets_fwd at the same tau.  weights may be NULL.  Exactly one
+ *   of sub_sets and sub_rows is non-null, else TREX_E_ARG.  Workspaces:
+ *   trex_nni_workspace_bytes / trex_attach_workspace_bytes.
+ * ---------------------------------------------------------------------- */
+int64_t trex_sets_fwd_workspace_bytes(int B, int L, int n_all, int Q);
+int trex_sankoff_sets_fwd(const int32_t* attach_plan, const int32_t* leaf_sets, const float* cost,
+                          int B, int L, int n_all, int Q, float tau, unsigned flags, float* dp,
+                          float* site_score, float* tree_score, void* workspace,
+                          int64_t workspace_bytes, void* stream);
+int trex_sankoff_sets_outside(const int32_t* nni_plan, const int32_t* leaf_sets,
+                              const float* cost, int B, int L, int n_all, int Q, float tau,
+                              const float* dp, float* outside, void* stream);
+int trex_sankoff_sets_nni_w(const int32_t* nni_plan, const int32_t* leaf_sets, const float* cost,
+                            int B, int L, int n_all, int Q, float tau, const float* dp,
+                            const float* outside, const float* weights, float* nni_score,
+                            void* workspace, int64_t workspace_bytes, void* stream);
+int trex_sankoff_sets_attach_w(const int32_t* attach_plan, const int32_t* leaf_sets,
+                               const float* cost, int B, int L, int n_all, int Q, float tau,
+                               const float* dp, const float* outside, const int32_t* sub_sets,
+                               const float* sub_rows, const float* weights, float* attach_score,
+                               void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ========================================================================
  * Synthetic data on the device: trex's
  * generate_groundtruth (src/trex/ground_truth.py:112-197, mutate :20-52) and

@@ -6,6 +6,7 @@ land, ``trex.tree``) on top of hand-written HIP kernels for gfx950 in
 """
 
 from ._lib import LIB_PATH, TrexError, lib  # noqa: F401
+from .leafsets import encode_alignment, sets_from_codes  # noqa: F401
 from .sankoff import (  # noqa: F401
     SankoffEngine,
     backtrack_sankoff_jit,
@@ -49,4 +50,5 @@ __all__ = [
     "HillClimbResult", "insert_leaf", "relabel_leaves", "stepwise_addition", "StepwiseResult",
     "parsimony_search", "SearchResult", "compress_sites", "parsimony_ratchet", "RatchetResult",
     "bootstrap_weights", "bootstrap_search", "BootstrapResult", "clade_support",
+    "sets_from_codes", "encode_alignment",
 ]

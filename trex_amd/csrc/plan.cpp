@@ -654,7 +654,7 @@ extern "C" int trex_ragged_plan_build(const int32_t* children, const int32_t* n_
 }
 
 // ---------------------------------------------------------------------------
-// NNI plan (sankoff_nni.hip): the pre-order "outside" pass and the per-edge
+// NNI plan (sankoff_rows.h): the pre-order "outside" pass and the per-edge
 // neighbour scores.  Layout (ints): header [16] | per tree a region of
 // nni_tree_ints(ni) ints: pre-order entries [ni][4] | move entries
 // [ni - 1][4].
@@ -665,7 +665,8 @@ extern "C" int trex_ragged_plan_build(const int32_t* children, const int32_t* n_
 //     stored order, s = v's sibling
 //   descriptor: node_desc (trex_common.h), kind << 24 | index (kind 1: leaf
 //     index, 2: internal row)
-// Attach plan (sankoff_nni.hip, attach_score_kernel): the edges of every tree
+// Attach plan (sankoff_rows.h, attach_score_kernel; sankoff_sets.hip,
+// sets_fwd_kernel walks it as a post-order): the edges of every tree
 // grouped by their upper node.  Layout (ints): header [16] | per tree
 // [ni][4]: entry r = {internal row r, descriptor of child 0, descriptor of
 // child 1, 1 if r is the root else 0}, rows ascending, children in stored

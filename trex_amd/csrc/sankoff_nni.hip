@@ -1,476 +1,17 @@
-// NNI neighbour scores on the Sankoff DP table: the pre-order "outside" pass
-// and the O(Q^2) evaluation of every nearest-neighbour interchange per site
-// (DESIGN.md "NNI neighbour scoring").
-//
-// One tree, one site; (+) is min for tau = 0 and smin_tau for tau > 0;
-// C[parent][child]; D_x is node x's inside row (leaf: 0 at its code, 1e5
-// elsewhere; internal: the DP-table row):
-//   message       M_x[i] = (+)_j (C[i][j] + D_x[j])
-//   outside row   O_root = 0;  O_c[j] = (+)_i (C[i][j] + O_p[i] + M_s[i])
-//                 (p = c's parent, s = c's sibling)
-//   move (v, k)   swaps a_k of (a0, a1) = children[v] with v's sibling s
-//                 (u = v's parent):  D'_v = M_s + M_a(1-k),
-//                 site score = (+)_i (O_u[i] + M_ak[i] + M(D'_v)[i])
-// Both kernels give one 64-lane wave 64 consecutive sites of ONE tree (sites
-// on the lane axis), so the plan words (plan.cpp, NNI plan) and the cost
-// matrix are wave-uniform and read with scalar loads.  Q = 2, 3, 4 are
-// compile-time instantiations with every row in registers and one 8 / 12 /
-// 16-byte buffer access per row and lane; 4 < Q <= 20 runs the same code
-// padded to 20 states with wave-uniform guards on the live ones.  The softmin
-// is the stabilised form (row minimum subtracted).  Neighbour scores are
-// summed over a wave's sites in fp64 (fixed butterfly), the per-wave partials
-// over a tree's tiles in a fixed order by a second kernel: no float atomics,
-// bitwise reproducible.  With site weights (DESIGN.md "Site weights") a site's
-// score is multiplied by its weight in fp64 where it enters that sum and
-// nowhere else; the WT = false instantiations are the unweighted code.  The
-// attachment scores further down (a new leaf or a subtree's row on every edge
-// of a tree; DESIGN.md "Attachment scores") read the same two tables with the
-// same helpers.
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
-#include <cmath>
-
-#include "sankoff_dev.h"
-#include "trex_common.h"
-
-namespace trex {
-
-namespace {
-
-constexpr int kNniPadQ = kSiteMaxQ;  // the generic path's padded alphabet
-
-struct NniArgs {
-  const int* plan;  // the NNI plan's per-tree regions (past the header)
-  const int8_t* leaves;
-  const float* cost;
-  const float* dp;
-  float* outside;
-  double* part;  // [B * tiles][ni - 1][2]
-  int B, L, nl, ni, Q, tiles;
-  float a, bcoef;
-};
-
-// DYN = false: Q == QP at compile time, the matrix in SGPRs.  DYN = true: QP
-// padded states, the live ones are j < Q (wave-uniform), matrix entries are
-// scalar loads at their use.
-template <int QP, bool DYN>
-struct CostM {
-  float c[DYN ? 1 : QP][DYN ? 1 : QP];
-  cptr<float> p;
-  int Q;
-  __device__ __forceinline__ void load(const float* cost, int q) {
-    p = as_const(cost);
-    Q = q;
-    if constexpr (!DYN) {
-#pragma unroll
-      for (int i = 0; i < QP; ++i)
-#pragma unroll
-        for (int j = 0; j < QP; ++j) c[i][j] = p[i * QP + j];
-    }
-  }
-  __device__ __forceinline__ bool live(int j) const { return !DYN || j < Q; }
-  __device__ __forceinline__ float at(int i, int j) const {
-    if constexpr (DYN) return p[i * Q + j];
-    else return c[i][j];
-  }
-};
-
-// (+) over the live entries of x
-template <int QP, bool DYN, bool SOFT>
-__device__ __forceinline__ float oplus(const CostM<QP, DYN>& cm, float a, float bcoef,
-                                       const float (&x)[QP]) {
-  float mn = INFINITY;
-#pragma unroll
-  for (int j = 0; j < QP; ++j)
-    if (cm.live(j)) mn = fminf(mn, x[j]);
-  if constexpr (!SOFT) return mn;
-  float acc = 0.0f;
-#pragma unroll
-  for (int j = 0; j < QP; ++j)
-    if (cm.live(j)) acc += fast_exp2((mn - x[j]) * a);
-  return fmaf(-bcoef, fast_log2(acc), mn);
-}
-
-// m[i] = (+)_j (C[i][j] + d[j]);  TRANS: m[j] = (+)_i (C[i][j] + d[i])
-template <int QP, bool DYN, bool SOFT, bool TRANS = false>
-__device__ __forceinline__ void message(const CostM<QP, DYN>& cm, float a, float bcoef,
-                                        const float (&d)[QP], float (&m)[QP]) {
-#pragma unroll
-  for (int i = 0; i < QP; ++i) {
-    m[i] = 0.0f;
-    if (cm.live(i)) {
-      float x[QP];
-#pragma unroll
-      for (int j = 0; j < QP; ++j) {
-        x[j] = 0.0f;
-        if (cm.live(j)) x[j] = (TRANS ? cm.at(j, i) : cm.at(i, j)) + d[j];
-      }
-      m[i] = oplus<QP, DYN, SOFT>(cm, a, bcoef, x);
-    }
-  }
-}
-
-// one tree's DP-layout table ([row][L][Q]): the lane's site of a row
-template <int QP, bool DYN>
-struct Rows {
-  rsrc_t r;
-  const float* base;
-  int L, Q, site;
-  __device__ __forceinline__ void init(const float* tree_base, int ni, int L_, int Q_, int site_) {
-    base = tree_base;
-    L = L_;
-    Q = Q_;
-    site = site_;
-    if constexpr (!DYN) r = make_rsrc(tree_base, (uint32_t)((size_t)ni * L_ * QP * 4));
-  }
-  __device__ __forceinline__ void get(int row, float (&d)[QP]) const {
-    if constexpr (!DYN) {
-      bld_row<QP>(r, site * QP * 4, row * L * QP * 4, d);
-    } else {
-      const float* p = base + ((size_t)row * L + site) * Q;
-#pragma unroll
-      for (int j = 0; j < QP; ++j) d[j] = j < Q ? p[j] : 0.0f;
-    }
-  }
-  __device__ __forceinline__ void put(int row, const float (&d)[QP]) const {
-    if constexpr (!DYN) {
-      bst_row<QP>(r, site * QP * 4, row * L * QP * 4, d);
-    } else {
-      float* p = const_cast<float*>(base) + ((size_t)row * L + site) * Q;
-#pragma unroll
-      for (int j = 0; j < QP; ++j)
-        if (j < Q) p[j] = d[j];
-    }
-  }
-};
-
-// inside row of a plan descriptor (kind << 24 | index): a leaf's row from its
-// code, an internal node's from the DP table
-template <int QP, bool DYN>
-__device__ __forceinline__ void inside_row(int desc, const Rows<QP, DYN>& dp,
-                                           const int8_t* __restrict__ tree_leaves, int L, int site,
-                                           float (&d)[QP]) {
-  const int idx = desc & 0xFFFF;
-  if ((desc >> 24) == kKindLeaf) {
-    const int code = tree_leaves[(size_t)idx * L + site];
-#pragma unroll
-    for (int j = 0; j < QP; ++j) d[j] = code == j ? 0.0f : kSentinel;
-  } else {
-    dp.get(idx, d);
-  }
-}
-
-// Outside pass: a wave walks its tree's internal nodes in pre-order, reading
-// the parent's outside row it wrote earlier (same lane, same address) and the
-// sibling's inside row, writing the node's outside row.
-template <int QP, bool DYN, bool SOFT>
-__global__ __launch_bounds__(kWave) void nni_outside_kernel(const NniArgs A) {
-  const int lane = threadIdx.x;
-  const int b = blockIdx.x / A.tiles, tile = blockIdx.x % A.tiles;
-  const int l = tile * kWave + lane;
-  const bool on = l < A.L;
-  const int site = on ? l : A.L - 1;  // tail lanes recompute the last site, store nothing
-  CostM<QP, DYN> cm;
-  cm.load(A.cost, A.Q);
-  const size_t tree = (size_t)b * A.ni * A.L * A.Q;
-  Rows<QP, DYN> dp, out;
-  dp.init(A.dp + tree, A.ni, A.L, A.Q, site);
-  out.init(A.outside + tree, A.ni, A.L, A.Q, site);
-  const int8_t* lv = A.leaves + (size_t)b * A.nl * A.L;
-  const cptr<int> pre = as_const(A.plan) + (size_t)b * (8 * A.ni - 4);
-  for (int k = 0; k < A.ni; ++k) {
-    const I4 e = load_step(pre, k);
-    float oc[QP];
-    if (e.y < 0) {
-#pragma unroll
-      for (int j = 0; j < QP; ++j) oc[j] = 0.0f;
-    } else {
-      float t[QP], ds[QP], ms[QP];
-      out.get(e.y, t);
-      inside_row<QP, DYN>(e.z, dp, lv, A.L, site, ds);
-      message<QP, DYN, SOFT>(cm, A.a, A.bcoef, ds, ms);
-#pragma unroll
-      for (int i = 0; i < QP; ++i) t[i] += ms[i];
-      message<QP, DYN, SOFT, true>(cm, A.a, A.bcoef, t, oc);
-    }
-    if (on) out.put(e.x, oc);
-  }
-}
-
-// The lane's site weight as the fp64 factor of its site scores: one coalesced
-// 256-byte read per wave at the clamped site.  A tail lane holds the last
-// site's weight and is masked by a select where the sums are taken, so it adds
-// nothing whatever that weight is.  Unweighted: exactly 1.0 (x * 1.0 is exact).
-// The weights ([B][L], or null) are a kernel argument of their own behind the
-// argument record, so the WT = false kernels read the record they always read.
-template <bool WT>
-__device__ __forceinline__ double site_weight(const float* weights, int b, int L, int site) {
-  if constexpr (WT) return (double)weights[(size_t)b * L + site];
-  else return 1.0;
-}
-
-// Neighbour scores: per non-root internal v both moves' site scores, summed
-// over the wave's sites in fp64; lane 0 writes the two partials.
-template <int QP, bool DYN, bool SOFT, bool WT>
-__global__ __launch_bounds__(kWave) void nni_score_kernel(const NniArgs A,
-                                                          const float* weights) {
-  const int lane = threadIdx.x;
-  const int b = blockIdx.x / A.tiles, tile = blockIdx.x % A.tiles;
-  const int l = tile * kWave + lane;
-  const bool on = l < A.L;
-  const int site = on ? l : A.L - 1;
-  const double w = site_weight<WT>(weights, b, A.L, site);
-  CostM<QP, DYN> cm;
-  cm.load(A.cost, A.Q);
-  const size_t tree = (size_t)b * A.ni * A.L * A.Q;
-  Rows<QP, DYN> dp, out;
-  dp.init(A.dp + tree, A.ni, A.L, A.Q, site);
-  out.init(A.outside + tree, A.ni, A.L, A.Q, site);
-  const int8_t* lv = A.leaves + (size_t)b * A.nl * A.L;
-  const cptr<int> mv = as_const(A.plan) + (size_t)b * (8 * A.ni - 4) + 4 * A.ni;
-  double* part = A.part + (size_t)blockIdx.x * (A.ni - 1) * 2;
-  for (int e = 0; e < A.ni - 1; ++e) {
-    const I4 m = load_step(mv, e);
-    float ou[QP], d[QP], m0[QP], m1[QP], ms[QP];
-    out.get(m.x, ou);
-    inside_row<QP, DYN>(m.y, dp, lv, A.L, site, d);
-    message<QP, DYN, SOFT>(cm, A.a, A.bcoef, d, m0);
-    inside_row<QP, DYN>(m.z, dp, lv, A.L, site, d);
-    message<QP, DYN, SOFT>(cm, A.a, A.bcoef, d, m1);
-    inside_row<QP, DYN>(m.w, dp, lv, A.L, site, d);
-    message<QP, DYN, SOFT>(cm, A.a, A.bcoef, d, ms);
-    float sc[2];
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      // v keeps a(1-k) and takes s; u keeps v and takes ak
-      float dv[QP], mdv[QP], x[QP];
-#pragma unroll
-      for (int j = 0; j < QP; ++j) dv[j] = ms[j] + (k == 0 ? m1[j] : m0[j]);
-      message<QP, DYN, SOFT>(cm, A.a, A.bcoef, dv, mdv);
-#pragma unroll
-      for (int i = 0; i < QP; ++i) x[i] = ou[i] + (k == 0 ? m0[i] : m1[i]) + mdv[i];
-      sc[k] = oplus<QP, DYN, SOFT>(cm, A.a, A.bcoef, x);
-    }
-    const double s0 = wave_sum_lane0(on ? (double)sc[0] * w : 0.0);
-    const double s1 = wave_sum_lane0(on ? (double)sc[1] * w : 0.0);
-    if (lane == 0) {
-      part[2 * e] = s0;
-      part[2 * e + 1] = s1;
-    }
-  }
-}
-
-// score[b][e][k] = the tiles' partials summed in tile order, rounded to fp32
-__global__ __launch_bounds__(256) void nni_reduce_kernel(const double* __restrict__ part, int B,
-                                                         int tiles, int moves,
-                                                         float* __restrict__ score) {
-  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (t >= (int64_t)B * moves) return;
-  const int64_t b = t / moves, m = t % moves;
-  const double* p = part + b * tiles * moves + m;
-  double acc = 0.0;
-  for (int k = 0; k < tiles; ++k) acc += p[(int64_t)k * moves];
-  score[t] = (float)acc;
-}
-
-int nni_check_shape(const char* fn, int B, int L, int n_all, int Q, float tau) {
-  if (B <= 0 || L <= 0 || n_all < 3 || n_all > 65535 || n_all % 2 == 0 || Q < 2)
-    return set_error(TREX_E_ARG, "%s: bad shape B=%d L=%d n_all=%d Q=%d", fn, B, L, n_all, Q);
-  if (n_all < 5)
-    return set_error(TREX_E_TOPOLOGY, "%s: a tree of %d leaves has no NNI neighbours", fn,
-                     (n_all + 1) / 2);
-  if (Q > kSiteMaxQ)
-    return set_error(TREX_E_UNSUPPORTED, "%s: Q=%d > %d is not supported by the NNI kernels", fn,
-                     Q, kSiteMaxQ);
-  if (!nonneg_finite_f32(tau))
-    return set_error(TREX_E_ARG, "%s: tau must be finite and >= 0 (got %g)", fn, tau);
-  const int ni = n_all - (n_all + 1) / 2;
-  if ((int64_t)ni * L * Q * 4 > 0x7FFFFFF0LL)
-    return set_error(TREX_E_UNSUPPORTED, "%s: one tree's DP table exceeds 2 GiB", fn);
-  if ((int64_t)B * ((L + kWave - 1) / kWave) > 0x7FFFFFFF)
-    return set_error(TREX_E_ARG, "%s: grid too large", fn);
-  return TREX_OK;
-}
-
-void nni_fill(NniArgs& A, const int32_t* nni_plan, const int8_t* leaves, const float* cost, int B,
-              int L, int n_all, int Q, float tau, const float* dp, float* outside) {
-  A.plan = nni_plan + TREX_PLAN_HEADER_INTS;
-  A.leaves = leaves;
-  A.cost = cost;
-  A.dp = dp;
-  A.outside = outside;
-  A.part = nullptr;
-  A.B = B;
-  A.L = L;
-  A.nl = (n_all + 1) / 2;
-  A.ni = n_all - A.nl;
-  A.Q = Q;
-  A.tiles = (L + kWave - 1) / kWave;
-  tau_coefs(tau, &A.a, &A.bcoef);
-}
-
-template <int QP, bool DYN, bool SOFT>
-void nni_score_launch(hipStream_t st, const NniArgs& A, const float* w) {
-  const dim3 grid(A.B * A.tiles), block(kWave);
-  if (w) hipLaunchKernelGGL((nni_score_kernel<QP, DYN, SOFT, true>), grid, block, 0, st, A, w);
-  else hipLaunchKernelGGL((nni_score_kernel<QP, DYN, SOFT, false>), grid, block, 0, st, A, w);
-}
-
-template <bool SCORE, int QP, bool DYN>
-void nni_launch_q(bool soft, hipStream_t st, const NniArgs& A, const float* w) {
-  if constexpr (SCORE) {
-    if (soft) nni_score_launch<QP, DYN, true>(st, A, w);
-    else nni_score_launch<QP, DYN, false>(st, A, w);
-  } else {
-    const dim3 grid(A.B * A.tiles), block(kWave);
-    if (soft) hipLaunchKernelGGL((nni_outside_kernel<QP, DYN, true>), grid, block, 0, st, A);
-    else hipLaunchKernelGGL((nni_outside_kernel<QP, DYN, false>), grid, block, 0, st, A);
-  }
-}
-
-// w: the scoring kernel's site weights, or null (the outside pass has none)
-template <bool SCORE>
-void nni_launch(bool soft, hipStream_t st, const NniArgs& A, const float* w = nullptr) {
-  switch (A.Q) {
-    case 2: nni_launch_q<SCORE, 2, false>(soft, st, A, w); break;
-    case 3: nni_launch_q<SCORE, 3, false>(soft, st, A, w); break;
-    case 4: nni_launch_q<SCORE, 4, false>(soft, st, A, w); break;
-    default: nni_launch_q<SCORE, kNniPadQ, true>(soft, st, A, w); break;
-  }
-}
-
-// ---- attachment scores (DESIGN.md "Attachment scores") -------------------
-// Attaching a subtree with inside row D_new (message M_new) on the edge above
-// node x makes a new node w with children x and the subtree:
-//   x below p, sibling s:  D_w = M_x + M_new,
-//                          site score = (+)_i (O_p[i] + M_s[i] + M(D_w)[i])
-//   x the root:            site score = (+)_k (M_root[k] + M_new[k])
-struct AttachArgs {
-  NniArgs n;  // n.plan: the attach plan's per-tree regions; n.part: [B * tiles][n_all]
-  const int8_t* sub_codes;  // [B][L], or
-  const float* sub_rows;    // [B][L][Q]
-};
-
-__device__ __forceinline__ int desc_node(int desc, int nl) {
-  return (desc >> 24) == kKindLeaf ? (desc & 0xFFFF) : nl + (desc & 0xFFFF);
-}
-
-// A wave walks its tree's internal rows p: both child edges of p from O_p and
-// the children's messages, on the root row also the new-root entry; site sums
-// in fp64, lane 0 writes the partials at the edges' lower node ids.
-template <int QP, bool DYN, bool SOFT, bool WT>
-__global__ __launch_bounds__(kWave) void attach_score_kernel(const AttachArgs AA,
-                                                             const float* weights) {
-  const NniArgs& A = AA.n;
-  const int lane = threadIdx.x;
-  const int b = blockIdx.x / A.tiles, tile = blockIdx.x % A.tiles;
-  const int l = tile * kWave + lane;
-  const bool on = l < A.L;
-  const int site = on ? l : A.L - 1;
-  const double w = site_weight<WT>(weights, b, A.L, site);
-  CostM<QP, DYN> cm;
-  cm.load(A.cost, A.Q);
-  const size_t tree = (size_t)b * A.ni * A.L * A.Q;
-  Rows<QP, DYN> dp, out;
-  dp.init(A.dp + tree, A.ni, A.L, A.Q, site);
-  out.init(A.outside + tree, A.ni, A.L, A.Q, site);
-  const int8_t* lv = A.leaves + (size_t)b * A.nl * A.L;
-  const cptr<int> pl = as_const(A.plan) + (size_t)b * 4 * A.ni;
-  const int n_all = A.nl + A.ni;
-  double* part = A.part + (size_t)blockIdx.x * n_all;
-  float mn[QP];
-  {
-    float dn[QP];
-    if (AA.sub_codes) {
-      const int code = AA.sub_codes[(size_t)b * A.L + site];
-#pragma unroll
-      for (int j = 0; j < QP; ++j) dn[j] = code == j ? 0.0f : kSentinel;
-    } else {
-      Rows<QP, DYN> sub;
-      sub.init(AA.sub_rows + (size_t)b * A.L * A.Q, 1, A.L, A.Q, site);
-      sub.get(0, dn);
-    }
-    message<QP, DYN, SOFT>(cm, A.a, A.bcoef, dn, mn);
-  }
-  for (int r = 0; r < A.ni; ++r) {
-    const I4 e = load_step(pl, r);
-    float op[QP], d[QP], m0[QP], m1[QP];
-    out.get(e.x, op);
-    inside_row<QP, DYN>(e.y, dp, lv, A.L, site, d);
-    message<QP, DYN, SOFT>(cm, A.a, A.bcoef, d, m0);
-    inside_row<QP, DYN>(e.z, dp, lv, A.L, site, d);
-    message<QP, DYN, SOFT>(cm, A.a, A.bcoef, d, m1);
-    float sc[2];
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      // the edge above child k: w takes child k and the subtree, p keeps the other child
-      float dw[QP], mdw[QP], x[QP];
-#pragma unroll
-      for (int j = 0; j < QP; ++j) dw[j] = (k == 0 ? m0[j] : m1[j]) + mn[j];
-      message<QP, DYN, SOFT>(cm, A.a, A.bcoef, dw, mdw);
-#pragma unroll
-      for (int i = 0; i < QP; ++i) x[i] = op[i] + (k == 0 ? m1[i] : m0[i]) + mdw[i];
-      sc[k] = oplus<QP, DYN, SOFT>(cm, A.a, A.bcoef, x);
-    }
-    const double s0 = wave_sum_lane0(on ? (double)sc[0] * w : 0.0);
-    const double s1 = wave_sum_lane0(on ? (double)sc[1] * w : 0.0);
-    if (lane == 0) {
-      part[desc_node(e.y, A.nl)] = s0;
-      part[desc_node(e.z, A.nl)] = s1;
-    }
-    if (e.w) {  // a new root above the old one
-      float x[QP];
-      dp.get(e.x, d);
-      message<QP, DYN, SOFT>(cm, A.a, A.bcoef, d, m0);
-#pragma unroll
-      for (int i = 0; i < QP; ++i) x[i] = m0[i] + mn[i];
-      const float sr = oplus<QP, DYN, SOFT>(cm, A.a, A.bcoef, x);
-      const double s2 = wave_sum_lane0(on ? (double)sr * w : 0.0);
-      if (lane == 0) part[A.nl + e.x] = s2;
-    }
-  }
-}
-
-template <int QP, bool DYN, bool SOFT>
-void attach_score_launch(hipStream_t st, const AttachArgs& A, const float* w) {
-  const dim3 grid(A.n.B * A.n.tiles), block(kWave);
-  if (w) hipLaunchKernelGGL((attach_score_kernel<QP, DYN, SOFT, true>), grid, block, 0, st, A, w);
-  else hipLaunchKernelGGL((attach_score_kernel<QP, DYN, SOFT, false>), grid, block, 0, st, A, w);
-}
-
-template <int QP, bool DYN>
-void attach_launch_q(bool soft, hipStream_t st, const AttachArgs& A, const float* w) {
-  if (soft) attach_score_launch<QP, DYN, true>(st, A, w);
-  else attach_score_launch<QP, DYN, false>(st, A, w);
-}
-
-void attach_launch(bool soft, hipStream_t st, const AttachArgs& A, const float* w) {
-  switch (A.n.Q) {
-    case 2: attach_launch_q<2, false>(soft, st, A, w); break;
-    case 3: attach_launch_q<3, false>(soft, st, A, w); break;
-    case 4: attach_launch_q<4, false>(soft, st, A, w); break;
-    default: attach_launch_q<kNniPadQ, true>(soft, st, A, w); break;
-  }
-}
-
-}  // namespace
-
-}  // namespace trex
+// NNI neighbour scores and attachment scores on the Sankoff DP table for
+// leaves given as int8 codes: the entry points over the kernels of
+// sankoff_rows.h (DESIGN.md "NNI neighbour scoring", "Attachment scores",
+// "Site weights").  sankoff_sets.hip has the same entry points for leaves
+// given as state sets.
+#include "sankoff_rows.h"
 
 using namespace trex;
 
 extern "C" int trex_sankoff_outside(const int32_t* nni_plan, const int8_t* leaves,
                                     const float* cost, int B, int L, int n_all, int Q, float tau,
                                     const float* dp, float* outside, void* stream) {
-  const char* fn = "trex_sankoff_outside";
-  if (int e = nni_check_shape(fn, B, L, n_all, Q, tau)) return e;
-  if (!nni_plan || !leaves || !cost || !dp || !outside)
-    return set_error(TREX_E_ARG, "%s: null pointer argument", fn);
-  NniArgs A;
-  nni_fill(A, nni_plan, leaves, cost, B, L, n_all, Q, tau, dp, outside);
-  nni_launch<false>(tau > 0.0f, (hipStream_t)stream, A);
-  return hip_check(fn);
+  return outside_run("trex_sankoff_outside", nni_plan, leaves, cost, B, L, n_all, Q, tau, dp,
+                     outside, stream);
 }
 
 extern "C" int64_t trex_nni_workspace_bytes(int B, int L, int n_all, int Q) {
@@ -478,32 +19,6 @@ extern "C" int64_t trex_nni_workspace_bytes(int B, int L, int n_all, int Q) {
   const int64_t ni = n_all - (n_all + 1) / 2;
   return (int64_t)B * ((L + kWave - 1) / kWave) * (ni - 1) * 2 * 8 + 256;
 }
-
-namespace {
-
-int nni_run(const char* fn, const int32_t* nni_plan, const int8_t* leaves, const float* cost,
-            int B, int L, int n_all, int Q, float tau, const float* dp, const float* outside,
-            const float* weights, float* nni_score, void* workspace, int64_t workspace_bytes,
-            void* stream) {
-  if (int e = nni_check_shape(fn, B, L, n_all, Q, tau)) return e;
-  if (!nni_plan || !leaves || !cost || !dp || !outside || !nni_score || !workspace)
-    return set_error(TREX_E_ARG, "%s: null pointer argument", fn);
-  if (workspace_bytes < trex_nni_workspace_bytes(B, L, n_all, Q))
-    return set_error(TREX_E_ARG, "%s: workspace too small", fn);
-  NniArgs A;
-  nni_fill(A, nni_plan, leaves, cost, B, L, n_all, Q, tau, dp, const_cast<float*>(outside));
-  A.part = static_cast<double*>(workspace);
-  hipStream_t st = (hipStream_t)stream;
-  nni_launch<true>(tau > 0.0f, st, A, weights);
-  if (int e = hip_check(fn)) return e;
-  const int moves = (A.ni - 1) * 2;
-  const int64_t n = (int64_t)B * moves;
-  hipLaunchKernelGGL(nni_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
-                     A.part, B, A.tiles, moves, nni_score);
-  return hip_check(fn);
-}
-
-}  // namespace
 
 extern "C" int trex_sankoff_nni_w(const int32_t* nni_plan, const int8_t* leaves,
                                   const float* cost, int B, int L, int n_all, int Q, float tau,
@@ -518,8 +33,8 @@ extern "C" int trex_sankoff_nni(const int32_t* nni_plan, const int8_t* leaves, c
                                 int B, int L, int n_all, int Q, float tau, const float* dp,
                                 const float* outside, float* nni_score, void* workspace,
                                 int64_t workspace_bytes, void* stream) {
-  return nni_run("trex_sankoff_nni", nni_plan, leaves, cost, B, L, n_all, Q, tau, dp, outside,
-                 nullptr, nni_score, workspace, workspace_bytes, stream);
+  return nni_run<int8_t>("trex_sankoff_nni", nni_plan, leaves, cost, B, L, n_all, Q, tau, dp,
+                         outside, nullptr, nni_score, workspace, workspace_bytes, stream);
 }
 
 extern "C" int64_t trex_attach_workspace_bytes(int B, int L, int n_all, int Q) {
@@ -527,44 +42,14 @@ extern "C" int64_t trex_attach_workspace_bytes(int B, int L, int n_all, int Q) {
   return (int64_t)B * ((L + kWave - 1) / kWave) * n_all * 8 + 256;
 }
 
-namespace {
-
-int attach_run(const char* fn, const int32_t* attach_plan, const int8_t* leaves,
-               const float* cost, int B, int L, int n_all, int Q, float tau, const float* dp,
-               const float* outside, const int8_t* sub_codes, const float* sub_rows,
-               const float* weights, float* attach_score, void* workspace,
-               int64_t workspace_bytes, void* stream) {
-  if (int e = nni_check_shape(fn, B, L, n_all, Q, tau)) return e;
-  if (!attach_plan || !leaves || !cost || !dp || !outside || !attach_score || !workspace)
-    return set_error(TREX_E_ARG, "%s: null pointer argument", fn);
-  if ((sub_codes == nullptr) == (sub_rows == nullptr))
-    return set_error(TREX_E_ARG, "%s: exactly one of sub_codes and sub_rows must be given", fn);
-  if (workspace_bytes < trex_attach_workspace_bytes(B, L, n_all, Q))
-    return set_error(TREX_E_ARG, "%s: workspace too small", fn);
-  AttachArgs A;
-  nni_fill(A.n, attach_plan, leaves, cost, B, L, n_all, Q, tau, dp, const_cast<float*>(outside));
-  A.n.part = static_cast<double*>(workspace);
-  A.sub_codes = sub_codes;
-  A.sub_rows = sub_rows;
-  hipStream_t st = (hipStream_t)stream;
-  attach_launch(tau > 0.0f, st, A, weights);
-  if (int e = hip_check(fn)) return e;
-  const int64_t n = (int64_t)B * n_all;
-  hipLaunchKernelGGL(nni_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
-                     A.n.part, B, A.n.tiles, n_all, attach_score);
-  return hip_check(fn);
-}
-
-}  // namespace
-
 extern "C" int trex_sankoff_attach_w(const int32_t* attach_plan, const int8_t* leaves,
                                      const float* cost, int B, int L, int n_all, int Q, float tau,
                                      const float* dp, const float* outside,
                                      const int8_t* sub_codes, const float* sub_rows,
                                      const float* weights, float* attach_score, void* workspace,
                                      int64_t workspace_bytes, void* stream) {
-  return attach_run("trex_sankoff_attach_w", attach_plan, leaves, cost, B, L, n_all, Q, tau, dp,
-                    outside, sub_codes, sub_rows, weights, attach_score, workspace,
+  return attach_run("trex_sankoff_attach_w", "sub_codes", attach_plan, leaves, cost, B, L, n_all,
+                    Q, tau, dp, outside, sub_codes, sub_rows, weights, attach_score, workspace,
                     workspace_bytes, stream);
 }
 
@@ -573,7 +58,7 @@ extern "C" int trex_sankoff_attach(const int32_t* attach_plan, const int8_t* lea
                                    const float* dp, const float* outside, const int8_t* sub_codes,
                                    const float* sub_rows, float* attach_score, void* workspace,
                                    int64_t workspace_bytes, void* stream) {
-  return attach_run("trex_sankoff_attach", attach_plan, leaves, cost, B, L, n_all, Q, tau, dp,
-                    outside, sub_codes, sub_rows, nullptr, attach_score, workspace,
-                    workspace_bytes, stream);
+  return attach_run<int8_t>("trex_sankoff_attach", "sub_codes", attach_plan, leaves, cost, B, L,
+                            n_all, Q, tau, dp, outside, sub_codes, sub_rows, nullptr, attach_score,
+                            workspace, workspace_bytes, stream);
 }

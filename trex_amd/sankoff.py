@@ -65,6 +65,10 @@ class SankoffEngine:
     """Batched Sankoff for a fixed (topology batch, L, Q): the hot path.
 
     leaves: int8 (B, n_leaves, L) codes on the device; cost: float32 (Q, Q).
+    ``forward``, ``outside``, ``nni_scores`` and ``attach_scores`` also take
+    int32 leaves: state sets, bit j of a cell = state j is allowed there
+    (``sets_from_codes``, ``encode_alignment``; DESIGN.md "State-set leaves";
+    Q <= 20, proper rooted binary trees).  The adjoint has no state-set form.
     Everything is enqueued on torch's current stream; nothing synchronises.
     """
 
@@ -125,17 +129,44 @@ class SankoffEngine:
         node-state-site order)."""
         return table.transpose(2, 3) if self.site_major else table
 
-    def _check_inputs(self, leaves, cost):
+    def _check_inputs(self, leaves, cost, sets=False):
+        """``sets``: the caller also takes int32 state sets.  Returns whether
+        ``leaves`` are state sets."""
         torch = _torch()
         p = self.plan
-        if leaves.dtype != torch.int8 or tuple(leaves.shape) != (p.B, p.n_leaves, self.L):
-            raise ValueError(f"leaves must be int8 {(p.B, p.n_leaves, self.L)}, got "
+        is_sets = leaves.dtype == torch.int32
+        if is_sets and not sets:
+            raise ValueError("int32 state-set leaves are not supported here: the adjoint "
+                             "(backward, fwd_bwd, value_and_grad) and to_trex_layout take int8 "
+                             "codes only")
+        if ((leaves.dtype != torch.int8 and not is_sets)
+                or tuple(leaves.shape) != (p.B, p.n_leaves, self.L)):
+            raise ValueError(f"leaves must be int8 {(p.B, p.n_leaves, self.L)}"
+                             f"{' (codes) or int32 (state sets)' if sets else ''}, got "
                              f"{leaves.dtype} {tuple(leaves.shape)}")
         if cost.dtype != torch.float32 or tuple(cost.shape) != (self.Q, self.Q):
             raise ValueError(f"cost must be float32 ({self.Q}, {self.Q})")
         for t in (leaves, cost):
             if not t.is_contiguous() or t.device != self.device:
                 raise ValueError("inputs must be contiguous tensors on the engine's device")
+        if is_sets:
+            from ._lib import has_leaf_sets
+
+            if not has_leaf_sets():
+                raise RuntimeError(f"{lib()._name} has no state-set leaf entry points "
+                                   "(trex_sankoff_sets_fwd, _sets_outside, _sets_nni_w, "
+                                   "_sets_attach_w): rebuild libtrexhip.so")
+        return is_sets
+
+    def _sets_workspace(self):
+        """Per-tile partials of the state-set forward (no initialisation)."""
+        p = self.plan
+        nbytes = lib().trex_sets_fwd_workspace_bytes(p.B, self.L, p.n_all, self.Q)
+        ws = getattr(self, "_sets_ws", None)
+        if ws is None or ws.numel() < max(nbytes, 1):
+            ws = self._sets_ws = _torch().empty(max(nbytes, 1), dtype=_torch().uint8,
+                                                device=self.device)
+        return ws
 
     def _check_weights(self, weights):
         """Site weights: a contiguous float32 (B, L) tensor on the engine's
@@ -192,7 +223,7 @@ class SankoffEngine:
         selects how each site's score is taken from the root row, and the
         weighted total is the weighted sum of those site scores."""
         torch = _torch()
-        self._check_inputs(leaves, cost)
+        is_sets = self._check_inputs(leaves, cost, sets=True)
         if weights is not None:
             self._check_weights(weights)
             site_score = True
@@ -215,10 +246,17 @@ class SankoffEngine:
         if ts is None:
             ts = torch.empty((p.B,), dtype=torch.float32, device=self.device)
         flags = self._flags(hard_root)
-        check(lib().trex_sankoff_fwd(
-            ptr(self.plan_dev), p.slot_word, ptr(leaves), ptr(cost), p.B, self.L, p.n_all,
-            self.Q, float(tau), flags, ptr(dp_t), ptr(ss), ptr(ts), ptr(self.workspace),
-            self.workspace.numel(), stream_handle(self.device)))
+        if is_sets:
+            ws = self._sets_workspace()
+            check(lib().trex_sankoff_sets_fwd(
+                ptr(p.attach_device(self.device)), ptr(leaves), ptr(cost), p.B, self.L, p.n_all,
+                self.Q, float(tau), flags, ptr(dp_t), ptr(ss), ptr(ts), ptr(ws), ws.numel(),
+                stream_handle(self.device)))
+        else:
+            check(lib().trex_sankoff_fwd(
+                ptr(self.plan_dev), p.slot_word, ptr(leaves), ptr(cost), p.B, self.L, p.n_all,
+                self.Q, float(tau), flags, ptr(dp_t), ptr(ss), ptr(ts), ptr(self.workspace),
+                self.workspace.numel(), stream_handle(self.device)))
         if weights is not None:
             self.weighted_score(ss, weights, out=ts)
         return ForwardResult(ts, dp_t, ss)
@@ -318,11 +356,12 @@ class SankoffEngine:
         """Outside table (B, n_int, L, Q) of ``dp`` (a forward's table at the
         same tau): O_root = 0, O_c[j] = (+)_i (C[i][j] + O_p[i] + M_s[i])."""
         torch = _torch()
-        self._check_inputs(leaves, cost)
+        is_sets = self._check_inputs(leaves, cost, sets=True)
         self._check_table(dp, "dp")
         p = self.plan
         out = torch.empty(self.dp_shape, dtype=torch.float32, device=self.device)
-        check(lib().trex_sankoff_outside(
+        fn = lib().trex_sankoff_sets_outside if is_sets else lib().trex_sankoff_outside
+        check(fn(
             ptr(p.nni_device(self.device)), ptr(leaves), ptr(cost), p.B, self.L, p.n_all, self.Q,
             float(tau), ptr(dp), ptr(out), stream_handle(self.device)))
         return out
@@ -337,7 +376,7 @@ class SankoffEngine:
         All-ones weights give the bits of the unweighted call; the relative
         bar holds only for weights >= 0."""
         torch = _torch()
-        self._check_inputs(leaves, cost)
+        is_sets = self._check_inputs(leaves, cost, sets=True)
         if weights is not None:
             self._check_weights(weights)
         p = self.plan
@@ -357,7 +396,9 @@ class SankoffEngine:
         head = (ptr(p.nni_device(self.device)), ptr(leaves), ptr(cost), p.B, self.L, p.n_all,
                 self.Q, float(tau), ptr(dp), ptr(outside))
         tail = (ptr(score), ptr(ws), ws.numel(), stream_handle(self.device))
-        if weights is None:  # also what an older library under TREX_HIP_LIB has
+        if is_sets:
+            check(lib().trex_sankoff_sets_nni_w(*head, ptr(weights), *tail))
+        elif weights is None:  # also what an older library under TREX_HIP_LIB has
             check(lib().trex_sankoff_nni(*head, *tail))
         else:
             check(lib().trex_sankoff_nni_w(*head, ptr(weights), *tail))
@@ -368,19 +409,19 @@ class SankoffEngine:
         """Tree scores after attaching a subtree on every edge, float32
         (B, n_all): entry [b, x] is tree b with the subtree on the edge above
         node x (``insert_leaf(children[b], x)`` for a leaf; x = n_all - 1 is a
-        new root; plain score).  The subtree is ``new_leaf``, int8 (B, L) leaf
-        codes, or ``sub_rows``, float32 (B, L, Q) inside rows (a subtree's
+        new root; plain score).  The subtree is ``new_leaf``, (B, L) leaf
+        cells of ``leaves``' dtype (int8 codes or int32 sets), or ``sub_rows``, float32 (B, L, Q) inside rows (a subtree's
         root DP row).  Runs the forward and / or the outside pass when ``dp``
         / ``outside`` are not given.  ``weights`` (float32 (B, L), finite):
         site weights as in ``nni_scores``."""
         torch = _torch()
-        self._check_inputs(leaves, cost)
+        is_sets = self._check_inputs(leaves, cost, sets=True)
         if weights is not None:
             self._check_weights(weights)
         p = self.plan
         if (new_leaf is None) == (sub_rows is None):
             raise ValueError("give exactly one of new_leaf and sub_rows")
-        sub, dtype, shape = ((new_leaf, torch.int8, (p.B, self.L)) if sub_rows is None else
+        sub, dtype, shape = ((new_leaf, leaves.dtype, (p.B, self.L)) if sub_rows is None else
                              (sub_rows, torch.float32, (p.B, self.L, self.Q)))
         if (not hasattr(sub, "dtype") or sub.dtype != dtype or tuple(sub.shape) != shape
                 or not sub.is_contiguous() or sub.device != self.device):
@@ -403,7 +444,9 @@ class SankoffEngine:
         head = (ptr(p.attach_device(self.device)), ptr(leaves), ptr(cost), p.B, self.L, p.n_all,
                 self.Q, float(tau), ptr(dp), ptr(outside), ptr(new_leaf), ptr(sub_rows))
         tail = (ptr(score), ptr(ws), ws.numel(), stream_handle(self.device))
-        if weights is None:
+        if is_sets:
+            check(lib().trex_sankoff_sets_attach_w(*head, ptr(weights), *tail))
+        elif weights is None:
             check(lib().trex_sankoff_attach(*head, *tail))
         else:
             check(lib().trex_sankoff_attach_w(*head, ptr(weights), *tail))
@@ -419,6 +462,9 @@ class SankoffEngine:
         """engine dp table -> trex VmappedDPTable per tree: (B, L, n_all, Q)."""
         torch = _torch()
         p = self.plan
+        if leaves.dtype == torch.int32:
+            raise ValueError("to_trex_layout does not support int32 state-set leaves: the trex "
+                             "table's leaf rows are written from int8 codes")
         out = torch.empty((p.B, self.L, p.n_all, self.Q), dtype=torch.float32,
                           device=self.device)
         check(lib().trex_dp_to_trex_layout(ptr(dp), ptr(leaves), p.B, self.L, p.n_all, self.Q,

@@ -49,6 +49,14 @@ def _host_weights(weights, B, L):
     return np.ascontiguousarray(w, dtype=np.float32)
 
 
+def _leaf_tensor(leaves, device):
+    """Leaves on the device: int32 input stays int32 (state sets, DESIGN.md
+    "State-set leaves"), anything else becomes int8 codes."""
+    torch = _torch()
+    lv = torch.as_tensor(leaves)
+    return lv.to(device=device, dtype=torch.int32 if lv.dtype == torch.int32 else torch.int8)
+
+
 def _n_sites(leaves):
     return int(leaves.shape[-1] if hasattr(leaves, "shape") else np.shape(leaves)[-1])
 
@@ -75,7 +83,8 @@ def nni_hill_climb(children, leaves, cost, *, tau: float = 0.0, min_gain: float 
     """Steepest-descent NNI search, every tree of the batch on its own.
 
     children (B, n_all, 2) or (n_all, 2) proper rooted binary trees; leaves
-    int8 (B, n_leaves, L) or (n_leaves, L) (shared by all trees); cost (Q, Q).
+    int8 codes or int32 state sets (``encode_alignment``), (B, n_leaves, L) or
+    (n_leaves, L) (shared by all trees); cost (Q, Q).
     Each round scores all neighbours of every tree and takes the lowest (ties:
     the lowest (v, k)); the move is applied only if ``score_new < score -
     min_gain * |score|`` -- relative, and by default the 1e-5 parity bar of
@@ -98,7 +107,7 @@ def nni_hill_climb(children, leaves, cost, *, tau: float = 0.0, min_gain: float 
         raise ValueError(f"children must be (B, n_all, 2), got {ch.shape}")
     B, n_all, _ = ch.shape
     nl = (n_all + 1) // 2
-    lv = torch.as_tensor(leaves).to(device=device, dtype=torch.int8)
+    lv = _leaf_tensor(leaves, device)
     if lv.ndim == 2:
         lv = lv[None].expand(B, -1, -1)
     if lv.ndim != 3 or tuple(lv.shape[:2]) != (B, nl):
@@ -167,7 +176,8 @@ def stepwise_addition(leaves, cost, *, order=None, n_trees: int = 1, seed: int =
                       tau: float = 0.0, device=None, weights=None) -> StepwiseResult:
     """Starting trees by stepwise addition, B addition sequences in one batch.
 
-    leaves int8 (n, L), one alignment of n >= 3 taxa; cost (Q, Q), Q <= 20.
+    leaves int8 codes or int32 state sets (n, L), one alignment of n >= 3
+    taxa; cost (Q, Q), Q <= 20.
     ``order`` (B, n): each row a permutation of the taxa, the sequence in
     which tree b takes them; ``order=None``: tree 0 takes the taxa as given,
     trees 1 .. n_trees - 1 permutations drawn from
@@ -183,7 +193,7 @@ def stepwise_addition(leaves, cost, *, order=None, n_trees: int = 1, seed: int =
     """
     torch = _torch()
     device = torch.device(device) if device is not None else _default_device()
-    lv = torch.as_tensor(leaves).to(device=device, dtype=torch.int8)
+    lv = _leaf_tensor(leaves, device)
     if lv.ndim != 2 or lv.shape[0] < 3:
         raise ValueError(f"leaves must be (n >= 3, L), got {tuple(lv.shape)}")
     lv = lv.contiguous()
@@ -249,13 +259,15 @@ def compress_sites(leaves):
     (patterns (n, P) int8, counts (P,) float32, index (L,) int64) with the
     distinct columns in order of first occurrence, ``patterns[:, index] ==
     leaves`` and ``counts == bincount(index)``.  The missing code -1 is a
-    symbol like any other.  Host numpy; ``counts`` are the ``weights`` of the
-    scoring and search functions on ``patterns``."""
+    symbol like any other.  int32 leaves are state sets: the patterns are
+    int32 too and a cell's whole mask is the symbol.  Host numpy; ``counts``
+    are the ``weights`` of the scoring and search functions on ``patterns``."""
     lv = np.asarray(leaves)
     if lv.ndim != 2 or lv.shape[0] < 1 or lv.shape[1] < 1:
         raise ValueError(f"leaves must be (n, L), got {lv.shape}")
-    lv = np.ascontiguousarray(lv.astype(np.int8))
-    cols = np.ascontiguousarray(lv.T).view(np.dtype((np.void, lv.shape[0]))).reshape(-1)
+    lv = np.ascontiguousarray(lv.astype(np.int32 if lv.dtype == np.int32 else np.int8))
+    cols = np.ascontiguousarray(lv.T).view(np.dtype((np.void, lv.shape[0] * lv.itemsize)))
+    cols = cols.reshape(-1)
     _, first, inv = np.unique(cols, return_index=True, return_inverse=True)
     by_first = np.argsort(first, kind="stable")  # sorted patterns -> first-occurrence order
     rank = np.empty_like(by_first)
