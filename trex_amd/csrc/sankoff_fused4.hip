@@ -280,13 +280,28 @@ __device__ __forceinline__ void fused4_body(const KArgs& A, const int* prog_, fl
 
   // the DP rows a step re-reads are issued kAdjRing - 1 steps ahead, both
   // loads unconditionally (a row the step does not read is addressed past the
-  // buffer: no traffic, zeros) so every path issues the same number of VMEM ops
-  auto pf_rows = [&](int k, float (&nd)[2][Q]) __attribute__((always_inline)) {
-    int r0 = kF4NoRow, r1 = kF4NoRow;
-    if (k >= 0) {
-      r0 = prog[kF4RecInts * k + 5];
-      r1 = prog[kF4RecInts * k + 6];
-    }
+  // buffer: no traffic, zeros) so every path issues the same number of VMEM ops.
+  // The program words of the reverse sweep (a step's re-read rows, its flags
+  // and operand offsets) are read on the scalar pipe with no branch around the
+  // load (a step before record 0 reads record 0 and ignores it) one step before
+  // their first use, into rings with static indices
+  struct F4Rows {
+    int r0, r1;
+  };
+  struct F4Rev {
+    int flags, a0, a1, slot;
+  };
+  auto load_rows = [&](int k) __attribute__((always_inline)) {
+    const cptr<int> p = prog + kF4RecInts * max(k, 0);
+    return F4Rows{p[5], p[6]};
+  };
+  auto load_rev = [&](int k) __attribute__((always_inline)) {
+    const cptr<int> p = prog + kF4RecInts * max(k, 0);
+    return F4Rev{p[0], p[2], p[3], p[4]};
+  };
+  // live: the rows are those of a step (k >= 0)
+  auto pf_rows = [&](bool live, const F4Rows& w, float (&nd)[2][Q]) __attribute__((always_inline)) {
+    const int r0 = live ? w.r0 : kF4NoRow, r1 = live ? w.r1 : kF4NoRow;
     bld_row<Q, kAuxFusedLoad>(rdp, r0 >= 0 ? voff : 0x7FFFFFF0, max(r0, 0) * rowbytes, nd[0]);
     bld_row<Q, kAuxFusedLoad>(rdp, r1 >= 0 ? voff : 0x7FFFFFF0, max(r1, 0) * rowbytes, nd[1]);
   };
@@ -297,7 +312,13 @@ __device__ __forceinline__ void fused4_body(const KArgs& A, const int* prog_, fl
       float wr[Q];
 #pragma unroll
       for (int j = 0; j < Q; ++j) wr[j] = w[i * Q + j];
-      axpy<Q>(acc[i], g[i], wr);
+      // (g_i through an opaque copy: otherwise the compiler builds the four
+      // (g_i, g_i) pairs of the packed FMAs once per step, ahead of the class
+      // branches, eight moves in every step, where a pair made inside the
+      // leaf's block folds into the FMA's operand select; PERFLOG.md)
+      float gi = g[i];
+      asm volatile("" : "+v"(gi));
+      axpy<Q>(acc[i], gi, wr);
     }
   };
   // edge to an internal child: its cotangent to the bypass or to its slot
@@ -318,7 +339,11 @@ __device__ __forceinline__ void fused4_body(const KArgs& A, const int* prog_, fl
       wr_slot(off, gc);
     }
   };
-  auto bstep = [&](const F4Rec& s, float (&cd)[2][Q]) __attribute__((always_inline)) {
+  // ahead(): the scalar loads of the steps to come.  Called behind the step's
+  // first LDS reads; the compiler sinks the loads to the join between the two
+  // children's edges wherever they are written (PERFLOG.md), which still leaves
+  // child 1's edge and the next step's prefetch arithmetic ahead of their use
+  auto bstep = [&](const F4Rev& s, float (&cd)[2][Q], auto&& ahead) __attribute__((always_inline)) {
     const int fl = s.flags;
     float g[Q];
     if (fl & (kF4ToNext | kF4Root)) {
@@ -340,6 +365,7 @@ __device__ __forceinline__ void fused4_body(const KArgs& A, const int* prog_, fl
 #pragma unroll
       for (int i = 0; i < Q; ++i) g[i] = gc[i];
     }
+    ahead();
     // the children in stored order (the dC sums depend on it).  One loop for
     // every class: straight-line code per class (a leaf's weights read beside
     // the other child's edge, a cherry's two weight tables and its edge tables
@@ -360,23 +386,28 @@ __device__ __forceinline__ void fused4_body(const KArgs& A, const int* prog_, fl
     }
   };
   {
-    // ring of kRing row buffers, unrolled so every buffer index is static;
-    // the step records themselves are read one step ahead
+    // ring of kRing row buffers, unrolled so every buffer index is static.
+    // Position r runs step k - r on buf[r] and rv[r]; it issues the rows of
+    // step k - r - (kRing - 1) from rw[r] into the freed buffer, and loads the
+    // next step's record and the next prefetch's rows into the next position
     constexpr int kRing = kAdjRing;
     float buf[kRing][2][Q];
+    F4Rows rw[kRing];
+    F4Rev rv[kRing];
 #pragma unroll
-    for (int r = 0; r < kRing - 1; ++r) pf_rows(n_int - 1 - r, buf[r]);
-    F4Rec nxt = load_rec(prog, n_int - 1);
+    for (int r = 0; r < kRing - 1; ++r)
+      pf_rows(n_int - 1 - r >= 0, load_rows(n_int - 1 - r), buf[r]);
+    rw[0] = load_rows(n_int - kRing);
+    rv[0] = load_rev(n_int - 1);
     for (int k = n_int - 1; k >= 0; k -= kRing) {
 #pragma unroll
       for (int r = 0; r < kRing; ++r) {
-        // step k - r uses buf[r]; its freed predecessor takes the rows of
-        // step k - r - (kRing - 1)
-        pf_rows(k - r - (kRing - 1), buf[(r + kRing - 1) % kRing]);
+        pf_rows(k - r - (kRing - 1) >= 0, rw[r], buf[(r + kRing - 1) % kRing]);
         if (k - r < 0) break;
-        const F4Rec s = nxt;
-        if (k - r - 1 >= 0) nxt = load_rec(prog, k - r - 1);
-        bstep(s, buf[r]);
+        bstep(rv[r], buf[r], [&]() __attribute__((always_inline)) {
+          rw[(r + 1) % kRing] = load_rows(k - r - kRing);
+          rv[(r + 1) % kRing] = load_rev(k - r - 1);
+        });
       }
     }
   }
