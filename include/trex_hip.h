@@ -742,6 +742,67 @@ int trex_sankoff_sets_attach_w(const int32_t* attach_plan, const int32_t* leaf_s
                                const float* sub_rows, const float* weights, float* attach_score,
                                void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------
+ * SPR neighbour scores: the plain score of every subtree-pruning-and-
+ * regrafting neighbour of every tree of the batch, from the same dp and
+ * outside tables.  Move (v, x): v any node but the root, u its parent, s its
+ * sibling.  Prune: u disappears; s takes u's place under g = parent(u) with
+ * sibling t = sibling(u) (u the root: s is the root of the remaining tree
+ * T\v).  Regraft: a new node w with children {x, v} goes on the edge above x,
+ * x any node of T\v (x not in subtree(v), x != u; x the root of T\v: w is the
+ * new root).  x = s gives the tree back.  With a prime for rows of T\v and
+ * P = the proper ancestors of u:
+ *   inside    D'_y = D_y off P; D'_g = M_s + M_t; above that D'_y =
+ *             M(D'_c) + M_sib(c), c = y's child on the path; M'_y = M(D'_y)
+ *   outside   O'_y = O_y on P; 0 for the root of T\v; else, with p', s' = y's
+ *             parent and sibling in T\v,
+ *             O'_y[j] = (+)_i (C[i][j] + O'_p'[i] + M'_s'[i])
+ *   score     x below p', sibling s':
+ *               (+)_i (O'_p'[i] + M'_s'[i] + M(M'_x + M_v)[i])
+ *             x the root of T\v:  (+)_k (M'_x[k] + M_v[k])
+ * Per pruned node at most n_int - 1 row steps; every internal node has at
+ * most one changed row (D' on P, O' off it).  No flags (see the NNI scores).
+ * Added without a version bump (trex_version() stays 10).
+ *
+ * trex_spr_plan_build [host]: accepts what trex_nni_plan_build accepts, same
+ *   error codes.  spr_plan: int32 buffer of trex_spr_plan_ints(B, n_all) ints
+ *   (copy it to the device unchanged): header [TREX_PLAN_HEADER_INTS] (magic,
+ *   B, n_all, n_leaves, n_int), then per tree
+ *     node records [n_all][4] = {parent id (-1: the root), sibling id (-1:
+ *       the root), entry, exit}: entry / exit number a pre-order DFS from the
+ *       root over ALL nodes, children in stored order; exit = entry + the
+ *       node count of the subtree, so y is in subtree(x) iff entry_x <=
+ *       entry_y < exit_x (x an ancestor of y or y itself);
+ *     walk records [n_int][4] = {internal row, child 0 id, child 1 id, 0}:
+ *       the internal nodes by ascending entry (a parent before its children),
+ *       children in stored order.
+ *   Node ids, not descriptors: id < n_leaves is a leaf, else row id - n_leaves.
+ * trex_sankoff_spr_w / trex_sankoff_sets_spr_w (int8 codes / int32 masks):
+ *   spr_score fp32 [B][n_all - 1][n_all]: entry [b][v][x] = the tree score
+ *   after move (v, x); +inf where the move does not exist (x in subtree(v),
+ *   x = u).  Every entry is written by every call.  weights may be NULL.
+ *   Shapes, the Q <= 20 limit, the tau check, the 2 GiB table limit and the
+ *   fp64 fixed-order site sums are those of trex_sankoff_nni_w; repeated calls
+ *   are bitwise equal.  workspace >= trex_spr_workspace_bytes bytes =
+ *   roundup(B tiles (n_all - 1) n_all 8, 256) + B tiles n_int 64 Q 4 + 256
+ *   (tiles = ceil(L / 64): per-tile fp64 partials, then per tile one changed
+ *   row per internal node and lane), no initialisation needed and nothing in
+ *   it is read before it is written.  trex_spr_workspace_bytes returns 0 for a
+ *   shape the calls refuse; sizes are computed in int64 and a shape whose
+ *   workspace or entry count would overflow is TREX_E_UNSUPPORTED.
+ * ---------------------------------------------------------------------- */
+int64_t trex_spr_plan_ints(int B, int n_all);
+int trex_spr_plan_build(const int32_t* children, int B, int n_all, int32_t* spr_plan);
+int64_t trex_spr_workspace_bytes(int B, int L, int n_all, int Q);
+int trex_sankoff_spr_w(const int32_t* spr_plan, const int8_t* leaves, const float* cost, int B,
+                       int L, int n_all, int Q, float tau, const float* dp, const float* outside,
+                       const float* weights, float* spr_score, void* workspace,
+                       int64_t workspace_bytes, void* stream);
+int trex_sankoff_sets_spr_w(const int32_t* spr_plan, const int32_t* leaf_sets, const float* cost,
+                            int B, int L, int n_all, int Q, float tau, const float* dp,
+                            const float* outside, const float* weights, float* spr_score,
+                            void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ========================================================================
  * Synthetic data on the device: trex's
  * generate_groundtruth (src/trex/ground_truth.py:112-197, mutate :20-52) and

@@ -6,8 +6,9 @@
 //     exactly by trex_plan_ints / trex_ragged_plan_ints, the fused Q = 4
 //     program (trex_fused4_program_build) of every accepted uniform plan, its
 //     accepted records range-checked, and the NNI planner
-//     (trex_nni_plan_build) and the attach planner (trex_attach_plan_build) on
-//     the same trees, their accepted plans range-checked;
+//     (trex_nni_plan_build), the attach planner (trex_attach_plan_build) and
+//     the SPR planner (trex_spr_plan_build) on the same trees, their accepted
+//     plans range-checked;
 //   * oracle/cpu_port.c -- the OpenMP C restatement (the CPU baseline and a
 //     test checker) on random trees, Q = 2..20, hard and softmin, with and
 //     without the DP table output.
@@ -233,6 +234,78 @@ int check_attach() {
   return 0;
 }
 
+// the SPR planner accepts the same trees as the NNI planner; an accepted
+// plan's node records nest like the tree (a node's interval inside its
+// parent's, siblings' intervals adjacent) and its walk lists every internal
+// row once, a parent before its children
+int check_spr() {
+  int built = 0, refused = 0;
+  for (int it = 0; it < 400; ++it) {
+    const int nl = rnd(2, 128);
+    const int n_all = 2 * nl - 1;
+    const int ni = n_all - nl;
+    const int B = rnd(1, 6);
+    std::vector<int32_t> ch((size_t)B * n_all * 2);
+    bool clean = true;
+    for (int b = 0; b < B; ++b) {
+      random_tree(nl, ch.data() + (size_t)b * n_all * 2);
+      if (it % 2) {
+        const int mode = rnd(0, 4);
+        perturb(nl, ch.data() + (size_t)b * n_all * 2, mode);
+        clean = clean && mode == 4;
+      }
+      if (it % 16 == 3 && nl >= 4) {  // a cycle: a node lists its ancestor, the root
+        ch[(size_t)b * n_all * 2 + 2 * nl] = n_all - 1;
+        clean = false;
+      }
+    }
+    const int64_t per = 4LL * n_all + 4LL * ni;
+    const int64_t n = trex_spr_plan_ints(B, n_all);
+    if (n != TREX_PLAN_HEADER_INTS + B * per) return 26;
+    std::vector<int32_t> plan((size_t)n), nni((size_t)trex_nni_plan_ints(B, n_all));
+    const int rc = trex_spr_plan_build(ch.data(), B, n_all, plan.data());
+    if (rc != 0 && rc != TREX_E_TOPOLOGY && rc != TREX_E_ARG) return 27;
+    if (rc != trex_nni_plan_build(ch.data(), B, n_all, nni.data())) return 28;  // same rule
+    if (clean && nl >= 3 && rc != 0) return 29;
+    if (nl < 3 && rc == 0) return 30;
+    if (rc != 0) {
+      ++refused;
+      continue;
+    }
+    ++built;
+    for (int b = 0; b < B; ++b) {
+      const int32_t* node = plan.data() + TREX_PLAN_HEADER_INTS + (size_t)b * per;
+      const int32_t* walk = node + 4 * n_all;
+      if (node[4 * (n_all - 1)] != -1 || node[4 * (n_all - 1) + 1] != -1 ||
+          node[4 * (n_all - 1) + 2] != 0 || node[4 * (n_all - 1) + 3] != n_all)
+        return 31;
+      for (int x = 0; x < n_all - 1; ++x) {
+        const int32_t* r = node + 4 * x;
+        if (r[0] <= x || r[0] < nl || r[0] >= n_all || r[1] < 0 || r[1] >= n_all || r[1] == x)
+          return 32;
+        const int32_t* p = node + 4 * r[0];
+        const int32_t* s = node + 4 * r[1];
+        if (s[0] != r[0] || s[1] != x) return 33;
+        if (r[2] <= p[2] || r[3] > p[3] || r[3] <= r[2] || (x < nl && r[3] != r[2] + 1)) return 34;
+        if (r[3] != s[2] && s[3] != r[2]) return 35;  // the two intervals share a border
+      }
+      std::vector<int> seen(ni, 0);
+      int last = -1;
+      for (int k = 0; k < ni; ++k) {
+        const int32_t* w = walk + 4 * k;
+        if (w[0] < 0 || w[0] >= ni || seen[w[0]]++ || w[3] != 0) return 36;
+        const int x = nl + w[0];
+        if (node[4 * x + 2] <= last) return 37;  // ascending entry
+        last = node[4 * x + 2];
+        for (int c = 1; c <= 2; ++c)
+          if (w[c] < 0 || w[c] >= x || node[4 * w[c]] != x) return 38;
+      }
+    }
+  }
+  std::printf("spr plans: %d built, %d refused\n", built, refused);
+  return 0;
+}
+
 int check_ragged() {
   for (int it = 0; it < 200; ++it) {
     const int B = rnd(1, 8);
@@ -297,6 +370,7 @@ int main() {
   if (int e = check_cpu_port()) return e;
   if (int e = check_nni()) return e;
   if (int e = check_attach()) return e;
+  if (int e = check_spr()) return e;
   std::printf("sanitize ok\n");
   return 0;
 }

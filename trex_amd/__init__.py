@@ -30,11 +30,13 @@ from .search import (  # noqa: F401
     nni_hill_climb,
     parsimony_ratchet,
     parsimony_search,
+    spr_hill_climb,
     stepwise_addition,
 )
 from .topology import (  # noqa: F401
     TreePlan,
     apply_nni,
+    apply_spr,
     children_from_adjacency,
     create_balanced_binary_tree,
     insert_leaf,
@@ -50,5 +52,5 @@ __all__ = [
     "HillClimbResult", "insert_leaf", "relabel_leaves", "stepwise_addition", "StepwiseResult",
     "parsimony_search", "SearchResult", "compress_sites", "parsimony_ratchet", "RatchetResult",
     "bootstrap_weights", "bootstrap_search", "BootstrapResult", "clade_support",
-    "sets_from_codes", "encode_alignment",
+    "sets_from_codes", "encode_alignment", "apply_spr", "spr_hill_climb",
 ]

@@ -78,6 +78,14 @@ SIGNATURES = {
                                        _p, _c_i64, _p]),
     "trex_sankoff_sets_attach_w": (_c_i, [_p, _p, _p, _c_i, _c_i, _c_i, _c_i, _c_f, _p, _p, _p,
                                           _p, _p, _p, _p, _c_i64, _p]),
+    # SPR neighbour scores (OPTIONAL below)
+    "trex_spr_plan_ints": (_c_i64, [_c_i, _c_i]),
+    "trex_spr_plan_build": (_c_i, [_p, _c_i, _c_i, _p]),
+    "trex_spr_workspace_bytes": (_c_i64, [_c_i, _c_i, _c_i, _c_i]),
+    "trex_sankoff_spr_w": (_c_i, [_p, _p, _p, _c_i, _c_i, _c_i, _c_i, _c_f, _p, _p, _p, _p, _p,
+                                  _c_i64, _p]),
+    "trex_sankoff_sets_spr_w": (_c_i, [_p, _p, _p, _c_i, _c_i, _c_i, _c_i, _c_f, _p, _p, _p, _p,
+                                       _p, _c_i64, _p]),
     # multi-GPU exchange (RCCL, dlopen'ed on first use)
     "trex_comm_unique_id_bytes": (_c_i, []),
     "trex_comm_get_unique_id": (_c_i, [_p]),
@@ -174,14 +182,16 @@ SIGNATURES = {
 
 # entry points added without a version bump: a library named by TREX_HIP_LIB
 # may be an older v10 build without them (tools/ab.sh runs a parent commit's
-# library under this package); has_fused4(), has_site_weights() and
-# has_leaf_sets() tell
+# library under this package); has_fused4(), has_site_weights(),
+# has_leaf_sets() and has_spr() tell
 _FUSED4 = ("trex_fused4_program_ints", "trex_fused4_program_build", "trex_sankoff_fwd_bwd_prog")
 _SITE_WEIGHTS = ("trex_site_weighted_sum", "trex_sankoff_nni_w", "trex_sankoff_attach_w")
 _LEAF_SETS = ("trex_sets_fwd_workspace_bytes", "trex_sankoff_sets_fwd",
               "trex_sankoff_sets_outside", "trex_sankoff_sets_nni_w",
               "trex_sankoff_sets_attach_w")
-OPTIONAL = _FUSED4 + _SITE_WEIGHTS + _LEAF_SETS
+_SPR = ("trex_spr_plan_ints", "trex_spr_plan_build", "trex_spr_workspace_bytes",
+        "trex_sankoff_spr_w", "trex_sankoff_sets_spr_w")
+OPTIONAL = _FUSED4 + _SITE_WEIGHTS + _LEAF_SETS + _SPR
 
 
 def has_fused4() -> bool:
@@ -197,6 +207,11 @@ def has_site_weights() -> bool:
 def has_leaf_sets() -> bool:
     """The loaded library has the state-set leaf entry points."""
     return all(hasattr(lib(), name) for name in _LEAF_SETS)
+
+
+def has_spr() -> bool:
+    """The loaded library has the SPR plan and scoring entry points."""
+    return all(hasattr(lib(), name) for name in _SPR)
 
 
 class TrexError(RuntimeError):

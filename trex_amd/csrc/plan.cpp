@@ -747,7 +747,44 @@ const char* attach_one_tree(const int32_t* ch, int n_all, int32_t* region) {
   return nullptr;
 }
 
-// both builders: header | one region of tree_ints per tree, written by one_tree
+// SPR plan (sankoff_spr.hip; layout: include/trex_hip.h): per node its parent,
+// sibling and the entry / exit numbers of a pre-order DFS over all nodes
+// (children in stored order), then the internal nodes by ascending entry with
+// their children's ids
+const char* spr_one_tree(const int32_t* ch, int n_all, int32_t* region) {
+  const int nl = tree_nl(n_all), ni = n_all - nl;
+  std::vector<int> parent;
+  if (const char* why = proper_tree_parents(ch, n_all, parent)) return why;
+  int32_t* node = region;
+  int32_t* walk = region + 4LL * n_all;
+  std::vector<int> st;
+  st.push_back(n_all - 1);
+  int entry = 0, w = 0;
+  while (!st.empty()) {
+    const int x = st.back();
+    st.pop_back();
+    const int p = parent[x];
+    node[4 * x] = p;
+    node[4 * x + 1] = p < 0 ? -1 : (ch[2 * p] == x ? ch[2 * p + 1] : ch[2 * p]);
+    node[4 * x + 2] = entry++;
+    if (x < nl) continue;
+    walk[4 * w] = x - nl;
+    walk[4 * w + 1] = ch[2 * x];
+    walk[4 * w + 2] = ch[2 * x + 1];
+    walk[4 * w + 3] = 0;
+    ++w;
+    st.push_back(ch[2 * x + 1]);
+    st.push_back(ch[2 * x]);
+  }
+  if (w != ni || entry != n_all) return "a node is not reachable from the root";
+  // subtree sizes: children have lower ids than their parents
+  std::vector<int> size(n_all, 1);
+  for (int x = nl; x < n_all; ++x) size[x] += size[ch[2 * x]] + size[ch[2 * x + 1]];
+  for (int x = 0; x < n_all; ++x) node[4 * x + 3] = node[4 * x + 2] + size[x];
+  return nullptr;
+}
+
+// the builders: header | one region of tree_ints per tree, written by one_tree
 int proper_plan_build(const char* fn, const char* two_leaves, int32_t magic,
                       const int32_t* children, int B, int n_all, int32_t* plan,
                       int64_t (*tree_ints_of)(int),
@@ -792,4 +829,15 @@ extern "C" int trex_attach_plan_build(const int32_t* children, int B, int n_all,
   using namespace trex;
   return proper_plan_build("trex_attach_plan_build", "is not supported", kAttachMagic, children, B,
                            n_all, attach_plan, attach_tree_ints, attach_one_tree);
+}
+
+extern "C" int64_t trex_spr_plan_ints(int B, int n_all) {
+  if (!trex::uniform_shape(B, n_all)) return 0;
+  return TREX_PLAN_HEADER_INTS + B * trex::spr_tree_ints(trex::tree_ni(n_all));
+}
+
+extern "C" int trex_spr_plan_build(const int32_t* children, int B, int n_all, int32_t* spr_plan) {
+  using namespace trex;
+  return proper_plan_build("trex_spr_plan_build", "has no SPR neighbours", kSprMagic, children, B,
+                           n_all, spr_plan, spr_tree_ints, spr_one_tree);
 }

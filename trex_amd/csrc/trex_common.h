@@ -19,6 +19,9 @@ constexpr int32_t kF4Magic = 0x54524634;      // 'TRF4' trex_fused4_program_buil
 constexpr int32_t kRaggedMagic = 0x54525247;  // 'TRRG' trex_ragged_plan_build
 constexpr int32_t kNniMagic = 0x54524E4E;     // 'TRNN' trex_nni_plan_build
 constexpr int32_t kAttachMagic = 0x54524154;  // 'TRAT' trex_attach_plan_build
+constexpr int32_t kSprMagic = 0x54525350;     // 'TRSP' trex_spr_plan_build
+// SPR plan, ints per tree: node records [n_all][4] | walk records [n_int][4]
+inline int64_t spr_tree_ints(int ni) { return 12LL * ni + 4; }
 constexpr size_t kLdsPerCu = 160 * 1024;    // gfx950: LDS bytes of a CU, the most one workgroup can take
 
 // leaves / internal rows of a tree of n_all nodes

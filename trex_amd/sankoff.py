@@ -65,7 +65,7 @@ class SankoffEngine:
     """Batched Sankoff for a fixed (topology batch, L, Q): the hot path.
 
     leaves: int8 (B, n_leaves, L) codes on the device; cost: float32 (Q, Q).
-    ``forward``, ``outside``, ``nni_scores`` and ``attach_scores`` also take
+    ``forward``, ``outside``, ``nni_scores``, ``attach_scores`` and ``spr_scores`` also take
     int32 leaves: state sets, bit j of a cell = state j is allowed there
     (``sets_from_codes``, ``encode_alignment``; DESIGN.md "State-set leaves";
     Q <= 20, proper rooted binary trees).  The adjoint has no state-set form.
@@ -450,6 +450,40 @@ class SankoffEngine:
             check(lib().trex_sankoff_attach(*head, *tail))
         else:
             check(lib().trex_sankoff_attach_w(*head, ptr(weights), *tail))
+        return score
+
+    def spr_scores(self, leaves, cost, tau: float = 0.0, *, dp=None, outside=None, weights=None):
+        """Tree scores of all SPR neighbours, float32 (B, n_all - 1, n_all):
+        entry [b, v, x] is tree b after ``apply_spr(children[b], v, x)`` --
+        the subtree of v pruned and regrafted on the edge above x (plain
+        score); +inf where the move does not exist (x in subtree(v), x = v's
+        parent).  Entry [b, v, sibling(v)] is the tree's own score.  Leaves are
+        int8 codes or int32 state sets.  Runs the forward and / or the outside
+        pass when ``dp`` / ``outside`` are not given.  ``weights`` (float32
+        (B, L), finite): site weights as in ``nni_scores``."""
+        torch = _torch()
+        is_sets = self._check_inputs(leaves, cost, sets=True)
+        if weights is not None:
+            self._check_weights(weights)
+        p = self.plan
+        plan_dev = p.spr_device(self.device)
+        if dp is None:
+            if outside is not None:
+                raise ValueError("outside without the dp table it was computed from")
+            dp = self.forward(leaves, cost, tau).dp
+        self._check_table(dp, "dp")
+        if outside is None:
+            outside = self.outside(leaves, cost, tau, dp)
+        self._check_table(outside, "outside")
+        nbytes = lib().trex_spr_workspace_bytes(p.B, self.L, p.n_all, self.Q)
+        ws = getattr(self, "_spr_ws", None)
+        if ws is None or ws.numel() < max(nbytes, 1):
+            ws = self._spr_ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=self.device)
+        score = torch.empty((p.B, p.n_all - 1, p.n_all), dtype=torch.float32, device=self.device)
+        fn = lib().trex_sankoff_sets_spr_w if is_sets else lib().trex_sankoff_spr_w
+        check(fn(ptr(plan_dev), ptr(leaves), ptr(cost), p.B, self.L, p.n_all, self.Q, float(tau),
+                 ptr(dp), ptr(outside), ptr(weights), ptr(score), ptr(ws), ws.numel(),
+                 stream_handle(self.device)))
         return score
 
     def value_and_grad(self, leaves, cost, tau: float = 0.0, d_tree_score=None,

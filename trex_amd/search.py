@@ -1,5 +1,5 @@
-"""Tree search on the Sankoff engine: stepwise-addition starting trees and NNI
-hill climbing.
+"""Tree search on the Sankoff engine: stepwise-addition starting trees, NNI and
+SPR hill climbing.
 
 The reference scores one given tree per ``run_sankoff`` call
 (src/trex/sankoff.py:114-188) and has no search; this module adds the first
@@ -22,7 +22,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from .sankoff import SankoffEngine, _default_device, _torch
-from .topology import TreePlan, apply_nni, insert_leaf, relabel_leaves
+from .topology import TreePlan, apply_nni, apply_spr, insert_leaf, relabel_leaves
 
 
 @dataclass
@@ -78,26 +78,13 @@ def _site_weights(weights, B, L, device):
     return w.contiguous()
 
 
-def nni_hill_climb(children, leaves, cost, *, tau: float = 0.0, min_gain: float = 1e-5,
-                   max_rounds: int = 100, device=None, weights=None) -> HillClimbResult:
-    """Steepest-descent NNI search, every tree of the batch on its own.
-
-    children (B, n_all, 2) or (n_all, 2) proper rooted binary trees; leaves
-    int8 codes or int32 state sets (``encode_alignment``), (B, n_leaves, L) or
-    (n_leaves, L) (shared by all trees); cost (Q, Q).
-    Each round scores all neighbours of every tree and takes the lowest (ties:
-    the lowest (v, k)); the move is applied only if ``score_new < score -
-    min_gain * |score|`` -- relative, and by default the 1e-5 parity bar of
-    the kernels, so a gain inside their rounding is never taken.  The plan is
-    rebuilt for the batch after every round that moved a tree; the climb stops
-    when no tree moves or after ``max_rounds`` rounds of moves.
-
-    ``weights``: site weights, (L,) shared by all trees or (B, L) (pattern
-    counts from ``compress_sites``, a ratchet's reweighting, bootstrap
-    replicates).  Every score compared or returned is then the weighted one;
-    the acceptance rule is unchanged.  Given as numpy they are validated on
-    the host as finite and >= 0.
-    """
+def _hill_climb(neighbours, apply_move, children, leaves, cost, tau, min_gain, max_rounds, device,
+                weights) -> HillClimbResult:
+    """The steepest-descent climb ``nni_hill_climb`` and ``spr_hill_climb``
+    share.  ``neighbours(eng, leaves, cost, tau, dp, weights)``: the scores of
+    every tree's neighbours, (B, ...) with the moves on the trailing axes;
+    ``apply_move(children, nl, n_all, i)``: one tree after its move of
+    flattened index i."""
     torch = _torch()
     device = torch.device(device) if device is not None else _default_device()
     ch = np.array(children, dtype=np.int32, copy=True)
@@ -134,14 +121,14 @@ def nni_hill_climb(children, leaves, cost, *, tau: float = 0.0, min_gain: float 
     for b in range(B):
         history[b].append(float(score[b]))
     while rounds < max_rounds:
-        nb = eng.nni_scores(lv, c, tau, dp=f.dp, weights=w).cpu().numpy().reshape(B, -1)
-        best = nb.argmin(axis=1)  # first minimum: the lowest (v, k)
+        nb = neighbours(eng, lv, c, tau, f.dp, w).cpu().numpy().reshape(B, -1)
+        best = nb.argmin(axis=1)  # first minimum: the lowest flattened move
         moved = []
         for b in range(B):
             new = float(nb[b, best[b]])
             cur = float(score[b])
             if new < cur - min_gain * abs(cur):
-                ch[b] = apply_nni(ch[b], nl + int(best[b]) // 2, int(best[b]) % 2)
+                ch[b] = apply_move(ch[b], nl, n_all, int(best[b]))
                 moved.append(b)
         if not moved:
             break
@@ -152,6 +139,57 @@ def nni_hill_climb(children, leaves, cost, *, tau: float = 0.0, min_gain: float 
             n_moves[b] += 1
             history[b].append(float(score[b]))
     return HillClimbResult(ch, score.astype(np.float32), history, n_moves, rounds)
+
+
+def nni_hill_climb(children, leaves, cost, *, tau: float = 0.0, min_gain: float = 1e-5,
+                   max_rounds: int = 100, device=None, weights=None) -> HillClimbResult:
+    """Steepest-descent NNI search, every tree of the batch on its own.
+
+    children (B, n_all, 2) or (n_all, 2) proper rooted binary trees; leaves
+    int8 codes or int32 state sets (``encode_alignment``), (B, n_leaves, L) or
+    (n_leaves, L) (shared by all trees); cost (Q, Q).
+    Each round scores all neighbours of every tree and takes the lowest (ties:
+    the lowest (v, k)); the move is applied only if ``score_new < score -
+    min_gain * |score|`` -- relative, and by default the 1e-5 parity bar of
+    the kernels, so a gain inside their rounding is never taken.  The plan is
+    rebuilt for the batch after every round that moved a tree; the climb stops
+    when no tree moves or after ``max_rounds`` rounds of moves.
+
+    ``weights``: site weights, (L,) shared by all trees or (B, L) (pattern
+    counts from ``compress_sites``, a ratchet's reweighting, bootstrap
+    replicates).  Every score compared or returned is then the weighted one;
+    the acceptance rule is unchanged.  Given as numpy they are validated on
+    the host as finite and >= 0.
+    """
+    return _hill_climb(
+        lambda eng, lv, c, t, dp, w: eng.nni_scores(lv, c, t, dp=dp, weights=w),
+        lambda ch, nl, n_all, i: apply_nni(ch, nl + i // 2, i % 2),
+        children, leaves, cost, tau, min_gain, max_rounds, device, weights)
+
+
+def spr_hill_climb(children, leaves, cost, *, tau: float = 0.0, min_gain: float = 1e-5,
+                   max_rounds: int = 100, device=None, weights=None) -> HillClimbResult:
+    """Steepest-descent SPR search: ``nni_hill_climb`` with the SPR
+    neighbourhood.  Every round scores all (n_all - 1) n_all moves (v, x) of
+    every tree (``SankoffEngine.spr_scores``: one forward, one outside and one
+    SPR pass; moves that do not exist score +inf) and takes the lowest (ties:
+    the lowest flattened (v, x)) by ``apply_spr``.  Arguments, the acceptance
+    rule, ``weights`` and the result are those of ``nni_hill_climb``.  An SPR
+    local optimum is an NNI local optimum too."""
+    return _hill_climb(
+        lambda eng, lv, c, t, dp, w: eng.spr_scores(lv, c, t, dp=dp, weights=w),
+        lambda ch, nl, n_all, i: apply_spr(ch, i // n_all, i % n_all),
+        children, leaves, cost, tau, min_gain, max_rounds, device, weights)
+
+
+_CLIMBS = {"nni": nni_hill_climb, "spr": spr_hill_climb}
+
+
+def _climb(moves):
+    """The hill climb of a search function's ``moves`` argument."""
+    if moves not in _CLIMBS:
+        raise ValueError(f"moves must be 'nni' or 'spr', got {moves!r}")
+    return _CLIMBS[moves]
 
 
 @dataclass
@@ -239,14 +277,16 @@ def stepwise_addition(leaves, cost, *, order=None, n_trees: int = 1, seed: int =
 
 def parsimony_search(leaves, cost, *, n_trees: int, seed: int = 0, tau: float = 0.0,
                      min_gain: float = 1e-5, max_rounds: int = 100, device=None,
-                     weights=None) -> SearchResult:
+                     weights=None, moves: str = "nni") -> SearchResult:
     """``stepwise_addition`` over ``n_trees`` addition sequences, then
-    ``nni_hill_climb`` on its trees; ``weights`` ((L,) or (n_trees, L)) go to
+    ``nni_hill_climb`` (``moves="nni"``) or ``spr_hill_climb``
+    (``moves="spr"``) on its trees; ``weights`` ((L,) or (n_trees, L)) go to
     both."""
+    climb = _climb(moves)
     start = stepwise_addition(leaves, cost, n_trees=n_trees, seed=seed, tau=tau, device=device,
                               weights=weights)
-    r = nni_hill_climb(start.children, leaves, cost, tau=tau, min_gain=min_gain,
-                       max_rounds=max_rounds, device=device, weights=weights)
+    r = climb(start.children, leaves, cost, tau=tau, min_gain=min_gain, max_rounds=max_rounds,
+              device=device, weights=weights)
     return SearchResult(r.children, r.scores, r.history, r.n_moves, r.rounds, start.scores,
                         start.order)
 
@@ -289,7 +329,7 @@ class RatchetResult:
 def parsimony_ratchet(children, leaves, cost, *, weights=None, n_iter: int = 10,
                       frac: float = 0.25, seed: int = 0, tau: float = 0.0,
                       min_gain: float = 1e-5, max_rounds: int = 100,
-                      device=None) -> RatchetResult:
+                      device=None, moves: str = "nni") -> RatchetResult:
     """The parsimony ratchet on a batch of start trees, each on its own.
 
     ``children`` and ``leaves`` as for ``nni_hill_climb``; ``weights`` host
@@ -300,8 +340,10 @@ def parsimony_ratchet(children, leaves, cost, *, weights=None, n_iter: int = 10,
     mask)`` -- the drawn sites count twice -- and climbs the result under
     ``weights`` again.  The search goes on from that tree whatever its score;
     each tree keeps the best tree it has seen, replaced only by a strictly
-    lower score.
+    lower score.  ``moves``: every climb is ``nni_hill_climb`` ("nni") or
+    ``spr_hill_climb`` ("spr").
     """
+    climb = _climb(moves)
     if n_iter < 0:
         raise ValueError("n_iter must be >= 0")
     if not 0.0 <= frac <= 1.0:
@@ -314,15 +356,15 @@ def parsimony_ratchet(children, leaves, cost, *, weights=None, n_iter: int = 10,
     w0 = _host_weights(np.ones(L, np.float32) if weights is None else weights, B, L)
     kw = dict(tau=tau, min_gain=min_gain, max_rounds=max_rounds, device=device)
     rng = np.random.default_rng(seed)
-    r = nni_hill_climb(ch, leaves, cost, weights=w0, **kw)
+    r = climb(ch, leaves, cost, weights=w0, **kw)
     best_ch, best = r.children.copy(), r.scores.copy()
     history = [[float(s)] for s in best]
     n_improved = np.zeros(B, dtype=np.int64)
     cur = r.children
     for _ in range(n_iter):
         mask = rng.random((B, L)) < frac
-        up = nni_hill_climb(cur, leaves, cost, weights=w0 * (1.0 + mask).astype(np.float32), **kw)
-        r = nni_hill_climb(up.children, leaves, cost, weights=w0, **kw)
+        up = climb(cur, leaves, cost, weights=w0 * (1.0 + mask).astype(np.float32), **kw)
+        r = climb(up.children, leaves, cost, weights=w0, **kw)
         cur = r.children
         better = r.scores < best
         best_ch[better] = cur[better]
@@ -356,17 +398,20 @@ class BootstrapResult:
 
 def bootstrap_search(leaves, cost, *, n_replicates: int, weights=None, seed: int = 0,
                      tau: float = 0.0, min_gain: float = 1e-5, max_rounds: int = 100,
-                     device=None) -> BootstrapResult:
+                     device=None, moves: str = "nni") -> BootstrapResult:
     """One ``parsimony_search`` tree per bootstrap replicate, all replicates
     in the launches of one batch: tree b is built and climbed under row b of
     ``bootstrap_weights(weights, n_replicates, seed)`` (``weights``: the (L,)
     pattern counts of ``leaves``, None: ones).  ``clade_support`` of a
-    reference tree over ``result.search.children`` gives its support values."""
+    reference tree over ``result.search.children`` gives its support values.
+    ``moves``: as in ``parsimony_search``."""
+    _climb(moves)
     L = _n_sites(leaves)
     counts = np.ones(L, np.float32) if weights is None else weights
     bw = bootstrap_weights(counts, n_replicates, seed)
     res = parsimony_search(leaves, cost, n_trees=n_replicates, seed=seed, tau=tau,
-                           min_gain=min_gain, max_rounds=max_rounds, device=device, weights=bw)
+                           min_gain=min_gain, max_rounds=max_rounds, device=device, weights=bw,
+                           moves=moves)
     return BootstrapResult(res, bw)
 
 

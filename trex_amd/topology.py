@@ -203,6 +203,52 @@ def insert_leaf(children, x: int) -> np.ndarray:
     return _renumber(grown, root, {c: c for c in range(nl + 1)}, key)
 
 
+def apply_spr(children, v: int, x: int) -> np.ndarray:
+    """Child lists (n_all, 2) of the SPR neighbour (v, x) of one tree -- the
+    tree of ``SankoffEngine.spr_scores``' entry ``[v, x]``.
+
+    ``v`` is any node but the root, u its parent and s its sibling.  Prune: u
+    disappears and s takes its place (u the root: s is the root of what
+    remains).  Regraft: a new node w with children {x, v} goes on the edge
+    above ``x``, any node of the remaining tree (x the remaining root: w is
+    the new root); ``x = s`` gives the tree back.  Internal nodes are
+    renumbered by ``apply_nni``'s rule, the DFS ordering children by their old
+    ids, w taking x's place among its parent's children (as in
+    ``insert_leaf``).  ValueError for v the root, x in subtree(v) or x = u.
+    """
+    kids, nl, n_all = _proper_kids(children)
+    v, x = int(v), int(x)
+    if not 0 <= v < n_all - 1:
+        raise ValueError(f"v must be a node other than the root, in [0, {n_all - 1}), got {v}")
+    if not 0 <= x < n_all:
+        raise ValueError(f"x must be a node id in [0, {n_all}), got {x}")
+    u = next(node for node, pair in kids.items() if v in pair)
+    s = kids[u][0] if kids[u][1] == v else kids[u][1]
+    below, todo = set(), [v]
+    while todo:
+        node = todo.pop()
+        below.add(node)
+        todo.extend(kids.get(node, ()))
+    if x in below or x == u:
+        raise ValueError(f"move ({v}, {x}): x must not be in subtree(v) nor v's parent {u}")
+    del kids[u]
+    root = n_all - 1
+    if u == root:
+        root = s
+    else:
+        g = next(pair for pair in kids.values() if u in pair)
+        g[g.index(u)] = s
+    w = "w"
+    if x == root:
+        root = w
+    else:
+        p = next(pair for pair in kids.values() if x in pair)
+        p[p.index(x)] = w
+    kids[w] = [x, v]
+    key = lambda node: (x, 1) if node == w else (node, 0)  # noqa: E731
+    return _renumber(kids, root, {c: c for c in range(nl)}, key)
+
+
 def relabel_leaves(children, perm) -> np.ndarray:
     """Child lists of one tree with leaf j renamed ``perm[j]`` (a permutation
     of the leaf ids); internal nodes are renumbered by ``apply_nni``'s rule,
@@ -264,7 +310,7 @@ class TreePlan:
         self.backtrack_ok = int(info[1])
         self.n_dag_nodes = int(info[2])
         self.n_unreached = int(info[3])
-        self._dev = {"plan": {}, "nni": {}, "attach": {}}
+        self._dev = {"plan": {}, "nni": {}, "attach": {}, "spr": {}}
 
     # -- NNI plan (trex_nni_plan_build), built on first use ------------------
     @functools.cached_property
@@ -288,6 +334,23 @@ class TreePlan:
     def attach_device(self, device):
         """The attach plan as an int32 device tensor (cached per device)."""
         return device_copy(self._dev["attach"], self.attach_host, device)
+
+    # -- SPR plan (trex_spr_plan_build), built on first use ------------------
+    @functools.cached_property
+    def spr_host(self) -> np.ndarray:
+        """The SPR plan (include/trex_hip.h) as int32; TrexError as for
+        ``nni_host``."""
+        from ._lib import has_spr
+
+        if not has_spr():
+            raise RuntimeError(f"{lib()._name} has no SPR entry points (trex_spr_plan_build, "
+                               "trex_sankoff_spr_w, trex_sankoff_sets_spr_w): rebuild "
+                               "libtrexhip.so")
+        return _build_plan("spr_plan", "SPR plan", self.children, self.B, self.n_all)
+
+    def spr_device(self, device):
+        """The SPR plan as an int32 device tensor (cached per device)."""
+        return device_copy(self._dev["spr"], self.spr_host, device)
 
     @property
     def nni_table(self) -> np.ndarray:
