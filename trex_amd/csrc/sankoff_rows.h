@@ -1,8 +1,12 @@
-// Lane-per-site row kernels on the Sankoff DP table, shared by sankoff_nni.hip
-// (leaves as int8 codes) and sankoff_sets.hip (leaves as int32 state sets,
-// DESIGN.md "State-set leaves"): the pre-order "outside" pass, the O(Q^2)
-// evaluation of every nearest-neighbour interchange per site (DESIGN.md "NNI
-// neighbour scoring") and the attachment scores.  The leaf type LT is a
+// Lane-per-site row passes on the Sankoff DP table: what every pass shares (the
+// argument record PassArgs, the variant dispatcher with_variant, the entry
+// points' body run_pass, the shape and workspace arithmetic, the row helpers)
+// and the kernels that both leaf types use: the pre-order
+// "outside" pass, the O(Q^2) evaluation of every nearest-neighbour interchange
+// per site (DESIGN.md "NNI neighbour scoring") and the attachment scores.
+// Included by sankoff_nni.hip (int8 codes), sankoff_sets.hip (int32 state
+// sets, DESIGN.md "State-set leaves"; it adds the state-set forward) and
+// sankoff_spr.hip (the SPR kernel, both leaf types).  The leaf type LT is a
 // template parameter that reaches exactly one place, leaf_row: everything
 // else is one copy of the arithmetic.
 //
@@ -42,16 +46,37 @@ namespace trex {
 
 namespace {
 
-constexpr int kNniPadQ = kSiteMaxQ;  // the generic path's padded alphabet
+constexpr int kRowsPadQ = kSiteMaxQ;  // the generic path's padded alphabet
 
+// ---- shapes: one wave per 64-site tile of one tree; a pass scores `moves`
+// entries per tree and its waves write [B * tiles][moves] fp64 partials.  The
+// *_workspace_bytes functions and the reduce take the counts from here; a
+// kernel's `part` offset is blockIdx.x times the same product, spelled out.
+constexpr int tiles(int L) { return (L + kWave - 1) / kWave; }
+inline int nni_moves(int n_all) { return (tree_ni(n_all) - 1) * 2; }
+inline int attach_moves(int n_all) { return n_all; }
+inline int64_t spr_moves(int n_all) { return (int64_t)(n_all - 1) * n_all; }
+
+// the shapes for which the *_workspace_bytes functions answer (0 otherwise)
+inline bool workspace_shape_ok(int B, int L, int n_all, int Q) {
+  return !(B <= 0 || L <= 0 || n_all < 5 || n_all % 2 == 0 || Q < 2 || Q > kSiteMaxQ);
+}
+inline int64_t partials_workspace_bytes(int B, int L, int n_all, int Q, int64_t moves) {
+  if (!workspace_shape_ok(B, L, n_all, Q)) return 0;
+  return (int64_t)B * tiles(L) * moves * 8 + 256;
+}
+
+// The argument record of every pass.  plan: the pass's plan, its per-tree
+// regions (past the header); part: the pass's [B * tiles][moves] partials.
+// What only one pass takes rides behind it (AttachArgs, SprArgs, SetsFwdArgs).
 template <class LT>
-struct NniArgs {
-  const int* plan;  // the NNI plan's per-tree regions (past the header)
+struct PassArgs {
+  const int* plan;
   const LT* leaves;
   const float* cost;
   const float* dp;
-  float* outside;
-  double* part;  // [B * tiles][ni - 1][2]
+  float* outside;  // null in the state-set forward, which has none (SetsFwdArgs)
+  double* part;
   int B, L, nl, ni, Q, tiles;
   float a, bcoef;
 };
@@ -180,11 +205,27 @@ __device__ __forceinline__ void inside_row(int desc, const Rows<QP, DYN>& dp,
   }
 }
 
+// The lane's site weight as the fp64 factor of its site scores: one coalesced
+// 256-byte read per wave at the clamped site.  A tail lane holds the last
+// site's weight and is masked by a select where the sums are taken, so it adds
+// nothing whatever that weight is.  Unweighted: exactly 1.0 (x * 1.0 is exact).
+// The weights ([B][L], or null) are a kernel argument of their own behind the
+// argument record, so the WT = false kernels read the record they always read.
+template <bool WT>
+__device__ __forceinline__ double site_weight(const float* weights, int b, int L, int site) {
+  if constexpr (WT) return (double)weights[(size_t)b * L + site];
+  else return 1.0;
+}
+
+// The tail-lane rule of every kernel of this family: a lane past the last site
+// (!on) recomputes the last site (`site` is clamped), stores no row and no
+// site score, and is masked out of the wave sums by a select.
+//
 // Outside pass: a wave walks its tree's internal nodes in pre-order, reading
 // the parent's outside row it wrote earlier (same lane, same address) and the
 // sibling's inside row, writing the node's outside row.
 template <class LT, int QP, bool DYN, bool SOFT>
-__global__ __launch_bounds__(kWave) void nni_outside_kernel(const NniArgs<LT> A) {
+__global__ __launch_bounds__(kWave) void outside_kernel(const PassArgs<LT> A) {
   const int lane = threadIdx.x;
   const int b = blockIdx.x / A.tiles, tile = blockIdx.x % A.tiles;
   const int l = tile * kWave + lane;
@@ -217,22 +258,10 @@ __global__ __launch_bounds__(kWave) void nni_outside_kernel(const NniArgs<LT> A)
   }
 }
 
-// The lane's site weight as the fp64 factor of its site scores: one coalesced
-// 256-byte read per wave at the clamped site.  A tail lane holds the last
-// site's weight and is masked by a select where the sums are taken, so it adds
-// nothing whatever that weight is.  Unweighted: exactly 1.0 (x * 1.0 is exact).
-// The weights ([B][L], or null) are a kernel argument of their own behind the
-// argument record, so the WT = false kernels read the record they always read.
-template <bool WT>
-__device__ __forceinline__ double site_weight(const float* weights, int b, int L, int site) {
-  if constexpr (WT) return (double)weights[(size_t)b * L + site];
-  else return 1.0;
-}
-
 // Neighbour scores: per non-root internal v both moves' site scores, summed
 // over the wave's sites in fp64; lane 0 writes the two partials.
 template <class LT, int QP, bool DYN, bool SOFT, bool WT>
-__global__ __launch_bounds__(kWave) void nni_score_kernel(const NniArgs<LT> A,
+__global__ __launch_bounds__(kWave) void nni_score_kernel(const PassArgs<LT> A,
                                                           const float* weights) {
   const int lane = threadIdx.x;
   const int b = blockIdx.x / A.tiles, tile = blockIdx.x % A.tiles;
@@ -281,9 +310,9 @@ __global__ __launch_bounds__(kWave) void nni_score_kernel(const NniArgs<LT> A,
 }
 
 // score[b][e][k] = the tiles' partials summed in tile order, rounded to fp32
-__global__ __launch_bounds__(256) void nni_reduce_kernel(const double* __restrict__ part, int B,
-                                                         int tiles, int moves,
-                                                         float* __restrict__ score) {
+__global__ __launch_bounds__(256) void reduce_partials_kernel(const double* __restrict__ part,
+                                                              int B, int tiles, int moves,
+                                                              float* __restrict__ score) {
   const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (t >= (int64_t)B * moves) return;
   const int64_t b = t / moves, m = t % moves;
@@ -297,11 +326,42 @@ __global__ __launch_bounds__(256) void nni_reduce_kernel(const double* __restric
 inline void reduce_partials(hipStream_t st, const double* part, int B, int tiles, int moves,
                             float* score) {
   const int64_t n = (int64_t)B * moves;
-  hipLaunchKernelGGL(nni_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, part,
-                     B, tiles, moves, score);
+  hipLaunchKernelGGL(reduce_partials_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
+                     part, B, tiles, moves, score);
 }
 
-inline int nni_check_shape(const char* fn, int B, int L, int n_all, int Q, float tau) {
+// ---- host side of every pass ----------------------------------------------
+// A kernel variant as compile-time tags: Q = QP in registers or (DYN) padded to
+// QP states; (+) hard or soft; site weights or none.
+template <int QP_, bool SOFT_, bool WT_>
+struct Variant {
+  static constexpr int QP = QP_;
+  static constexpr bool DYN = QP_ > 4, SOFT = SOFT_, WT = WT_;
+};
+
+// f(Variant<...>()) for the call's (Q, soft, weighted).  A pass without a
+// weighted form passes weighted = false and has no WT parameter to instantiate.
+template <class F>
+void with_variant(int Q, bool soft, bool weighted, F&& f) {
+  auto rest = [&](auto qp) {
+    constexpr int QP = decltype(qp)::value;
+    if (soft) {
+      if (weighted) f(Variant<QP, true, true>());
+      else f(Variant<QP, true, false>());
+    } else {
+      if (weighted) f(Variant<QP, false, true>());
+      else f(Variant<QP, false, false>());
+    }
+  };
+  switch (Q) {
+    case 2: rest(std::integral_constant<int, 2>()); break;
+    case 3: rest(std::integral_constant<int, 3>()); break;
+    case 4: rest(std::integral_constant<int, 4>()); break;
+    default: rest(std::integral_constant<int, kRowsPadQ>()); break;
+  }
+}
+
+inline int pass_check_shape(const char* fn, int B, int L, int n_all, int Q, float tau) {
   if (B <= 0 || L <= 0 || n_all < 3 || n_all > 65535 || n_all % 2 == 0 || Q < 2)
     return set_error(TREX_E_ARG, "%s: bad shape B=%d L=%d n_all=%d Q=%d", fn, B, L, n_all, Q);
   if (n_all < 5)
@@ -312,62 +372,96 @@ inline int nni_check_shape(const char* fn, int B, int L, int n_all, int Q, float
                      Q, kSiteMaxQ);
   if (!nonneg_finite_f32(tau))
     return set_error(TREX_E_ARG, "%s: tau must be finite and >= 0 (got %g)", fn, tau);
-  const int ni = n_all - (n_all + 1) / 2;
-  if ((int64_t)ni * L * Q * 4 > 0x7FFFFFF0LL)
+  if ((int64_t)tree_ni(n_all) * L * Q * 4 > 0x7FFFFFF0LL)
     return set_error(TREX_E_UNSUPPORTED, "%s: one tree's DP table exceeds 2 GiB", fn);
-  if ((int64_t)B * ((L + kWave - 1) / kWave) > 0x7FFFFFFF)
+  if ((int64_t)B * tiles(L) > 0x7FFFFFFF)
     return set_error(TREX_E_ARG, "%s: grid too large", fn);
   return TREX_OK;
 }
 
+// An entry point's arguments.  A pass that lacks one leaves it null / 0:
+// outside (the state-set forward), weights, score and the workspace (the
+// outside pass, which sums nothing).
 template <class LT>
-void nni_fill(NniArgs<LT>& A, const int32_t* nni_plan, const LT* leaves, const float* cost, int B,
-              int L, int n_all, int Q, float tau, const float* dp, float* outside) {
-  A.plan = nni_plan + TREX_PLAN_HEADER_INTS;
-  A.leaves = leaves;
-  A.cost = cost;
-  A.dp = dp;
-  A.outside = outside;
-  A.part = nullptr;
-  A.B = B;
-  A.L = L;
-  A.nl = (n_all + 1) / 2;
-  A.ni = n_all - A.nl;
-  A.Q = Q;
-  A.tiles = (L + kWave - 1) / kWave;
-  tau_coefs(tau, &A.a, &A.bcoef);
+struct PassCall {
+  const char* fn;
+  const int32_t* plan;
+  const LT* leaves;
+  const float* cost;
+  int B, L, n_all, Q;
+  float tau;
+  const float* dp;
+  float* outside;
+  const float* weights;
+  float* score;  // [B][moves]
+  void* workspace;
+  int64_t workspace_bytes;
+  void* stream;
+};
+
+// The body of every entry point.  rest_given: the pass's own pointers besides
+// plan / leaves / cost / dp are non-null.  pre(need): the pass's own argument
+// checks, then the workspace bytes it needs.  moves: score entries per tree (0:
+// no partials to sum).  launch(A, stream): the pass's kernel on the filled
+// record.
+template <class LT, class Pre, class Launch>
+int run_pass(const PassCall<LT>& c, bool rest_given, Pre&& pre, int moves, Launch&& launch) {
+  if (int e = pass_check_shape(c.fn, c.B, c.L, c.n_all, c.Q, c.tau)) return e;
+  if (!c.plan || !c.leaves || !c.cost || !c.dp || !rest_given)
+    return set_error(TREX_E_ARG, "%s: null pointer argument", c.fn);
+  int64_t need = 0;
+  if (int e = pre(need)) return e;
+  if (c.workspace_bytes < need) return set_error(TREX_E_ARG, "%s: workspace too small", c.fn);
+  PassArgs<LT> A;
+  A.plan = c.plan + TREX_PLAN_HEADER_INTS;
+  A.leaves = c.leaves;
+  A.cost = c.cost;
+  A.dp = c.dp;
+  A.outside = c.outside;
+  A.part = static_cast<double*>(c.workspace);
+  A.B = c.B;
+  A.L = c.L;
+  A.nl = tree_nl(c.n_all);
+  A.ni = tree_ni(c.n_all);
+  A.Q = c.Q;
+  A.tiles = tiles(c.L);
+  tau_coefs(c.tau, &A.a, &A.bcoef);
+  hipStream_t st = (hipStream_t)c.stream;
+  launch(A, st);
+  if (int e = hip_check(c.fn)) return e;
+  if (moves == 0) return TREX_OK;
+  reduce_partials(st, A.part, c.B, A.tiles, moves, c.score);
+  return hip_check(c.fn);
 }
 
-template <class LT, int QP, bool DYN, bool SOFT>
-void nni_score_launch(hipStream_t st, const NniArgs<LT>& A, const float* w) {
-  const dim3 grid(A.B * A.tiles), block(kWave);
-  if (w)
-    hipLaunchKernelGGL((nni_score_kernel<LT, QP, DYN, SOFT, true>), grid, block, 0, st, A, w);
-  else
-    hipLaunchKernelGGL((nni_score_kernel<LT, QP, DYN, SOFT, false>), grid, block, 0, st, A, w);
+template <class LT>
+int outside_run(const PassCall<LT>& c) {
+  return run_pass(
+      c, c.outside != nullptr, [](int64_t&) { return TREX_OK; }, 0,
+      [&](const PassArgs<LT>& A, hipStream_t st) {
+        with_variant(c.Q, c.tau > 0.0f, false, [&](auto v) {
+          using V = decltype(v);
+          hipLaunchKernelGGL((outside_kernel<LT, V::QP, V::DYN, V::SOFT>), dim3(A.B * A.tiles),
+                             dim3(kWave), 0, st, A);
+        });
+      });
 }
 
-template <bool SCORE, class LT, int QP, bool DYN>
-void nni_launch_q(bool soft, hipStream_t st, const NniArgs<LT>& A, const float* w) {
-  if constexpr (SCORE) {
-    if (soft) nni_score_launch<LT, QP, DYN, true>(st, A, w);
-    else nni_score_launch<LT, QP, DYN, false>(st, A, w);
-  } else {
-    const dim3 grid(A.B * A.tiles), block(kWave);
-    if (soft) hipLaunchKernelGGL((nni_outside_kernel<LT, QP, DYN, true>), grid, block, 0, st, A);
-    else hipLaunchKernelGGL((nni_outside_kernel<LT, QP, DYN, false>), grid, block, 0, st, A);
-  }
-}
-
-// w: the scoring kernel's site weights, or null (the outside pass has none)
-template <bool SCORE, class LT>
-void nni_launch(bool soft, hipStream_t st, const NniArgs<LT>& A, const float* w = nullptr) {
-  switch (A.Q) {
-    case 2: nni_launch_q<SCORE, LT, 2, false>(soft, st, A, w); break;
-    case 3: nni_launch_q<SCORE, LT, 3, false>(soft, st, A, w); break;
-    case 4: nni_launch_q<SCORE, LT, 4, false>(soft, st, A, w); break;
-    default: nni_launch_q<SCORE, LT, kNniPadQ, true>(soft, st, A, w); break;
-  }
+template <class LT>
+int nni_run(const PassCall<LT>& c) {
+  return run_pass(
+      c, c.outside && c.score && c.workspace,
+      [&](int64_t& need) {
+        need = trex_nni_workspace_bytes(c.B, c.L, c.n_all, c.Q);
+        return TREX_OK;
+      },
+      nni_moves(c.n_all), [&](const PassArgs<LT>& A, hipStream_t st) {
+        with_variant(c.Q, c.tau > 0.0f, c.weights != nullptr, [&](auto v) {
+          using V = decltype(v);
+          hipLaunchKernelGGL((nni_score_kernel<LT, V::QP, V::DYN, V::SOFT, V::WT>),
+                             dim3(A.B * A.tiles), dim3(kWave), 0, st, A, c.weights);
+        });
+      });
 }
 
 // ---- attachment scores (DESIGN.md "Attachment scores") -------------------
@@ -377,8 +471,7 @@ void nni_launch(bool soft, hipStream_t st, const NniArgs<LT>& A, const float* w 
 //                          site score = (+)_i (O_p[i] + M_s[i] + M(D_w)[i])
 //   x the root:            site score = (+)_k (M_root[k] + M_new[k])
 template <class LT>
-struct AttachArgs {
-  NniArgs<LT> n;  // n.plan: the attach plan's per-tree regions; n.part: [B * tiles][n_all]
+struct AttachArgs : PassArgs<LT> {
   const LT* sub_codes;    // [B][L] leaf cells, or
   const float* sub_rows;  // [B][L][Q]
 };
@@ -393,7 +486,7 @@ __device__ __forceinline__ int desc_node(int desc, int nl) {
 template <class LT, int QP, bool DYN, bool SOFT, bool WT>
 __global__ __launch_bounds__(kWave) void attach_score_kernel(const AttachArgs<LT> AA,
                                                              const float* weights) {
-  const NniArgs<LT>& A = AA.n;
+  const PassArgs<LT>& A = AA;
   const int lane = threadIdx.x;
   const int b = blockIdx.x / A.tiles, tile = blockIdx.x % A.tiles;
   const int l = tile * kWave + lane;
@@ -461,89 +554,27 @@ __global__ __launch_bounds__(kWave) void attach_score_kernel(const AttachArgs<LT
   }
 }
 
-template <class LT, int QP, bool DYN, bool SOFT>
-void attach_score_launch(hipStream_t st, const AttachArgs<LT>& A, const float* w) {
-  const dim3 grid(A.n.B * A.n.tiles), block(kWave);
-  if (w)
-    hipLaunchKernelGGL((attach_score_kernel<LT, QP, DYN, SOFT, true>), grid, block, 0, st, A, w);
-  else
-    hipLaunchKernelGGL((attach_score_kernel<LT, QP, DYN, SOFT, false>), grid, block, 0, st, A, w);
-}
-
-template <class LT, int QP, bool DYN>
-void attach_launch_q(bool soft, hipStream_t st, const AttachArgs<LT>& A, const float* w) {
-  if (soft) attach_score_launch<LT, QP, DYN, true>(st, A, w);
-  else attach_score_launch<LT, QP, DYN, false>(st, A, w);
-}
-
-template <class LT>
-void attach_launch(bool soft, hipStream_t st, const AttachArgs<LT>& A, const float* w) {
-  switch (A.n.Q) {
-    case 2: attach_launch_q<LT, 2, false>(soft, st, A, w); break;
-    case 3: attach_launch_q<LT, 3, false>(soft, st, A, w); break;
-    case 4: attach_launch_q<LT, 4, false>(soft, st, A, w); break;
-    default: attach_launch_q<LT, kNniPadQ, true>(soft, st, A, w); break;
-  }
-}
-
-// ---- the entry points' bodies, for either leaf type ----------------------
-template <class LT>
-int outside_run(const char* fn, const int32_t* nni_plan, const LT* leaves, const float* cost,
-                int B, int L, int n_all, int Q, float tau, const float* dp, float* outside,
-                void* stream) {
-  if (int e = nni_check_shape(fn, B, L, n_all, Q, tau)) return e;
-  if (!nni_plan || !leaves || !cost || !dp || !outside)
-    return set_error(TREX_E_ARG, "%s: null pointer argument", fn);
-  NniArgs<LT> A;
-  nni_fill(A, nni_plan, leaves, cost, B, L, n_all, Q, tau, dp, outside);
-  nni_launch<false>(tau > 0.0f, (hipStream_t)stream, A);
-  return hip_check(fn);
-}
-
-template <class LT>
-int nni_run(const char* fn, const int32_t* nni_plan, const LT* leaves, const float* cost, int B,
-            int L, int n_all, int Q, float tau, const float* dp, const float* outside,
-            const float* weights, float* nni_score, void* workspace, int64_t workspace_bytes,
-            void* stream) {
-  if (int e = nni_check_shape(fn, B, L, n_all, Q, tau)) return e;
-  if (!nni_plan || !leaves || !cost || !dp || !outside || !nni_score || !workspace)
-    return set_error(TREX_E_ARG, "%s: null pointer argument", fn);
-  if (workspace_bytes < trex_nni_workspace_bytes(B, L, n_all, Q))
-    return set_error(TREX_E_ARG, "%s: workspace too small", fn);
-  NniArgs<LT> A;
-  nni_fill(A, nni_plan, leaves, cost, B, L, n_all, Q, tau, dp, const_cast<float*>(outside));
-  A.part = static_cast<double*>(workspace);
-  hipStream_t st = (hipStream_t)stream;
-  nni_launch<true>(tau > 0.0f, st, A, weights);
-  if (int e = hip_check(fn)) return e;
-  reduce_partials(st, A.part, B, A.tiles, (A.ni - 1) * 2, nni_score);
-  return hip_check(fn);
-}
-
 // sub_name: what the entry point calls its leaf-cell subtree argument
 template <class LT>
-int attach_run(const char* fn, const char* sub_name, const int32_t* attach_plan, const LT* leaves,
-               const float* cost, int B, int L, int n_all, int Q, float tau, const float* dp,
-               const float* outside, const LT* sub_codes, const float* sub_rows,
-               const float* weights, float* attach_score, void* workspace,
-               int64_t workspace_bytes, void* stream) {
-  if (int e = nni_check_shape(fn, B, L, n_all, Q, tau)) return e;
-  if (!attach_plan || !leaves || !cost || !dp || !outside || !attach_score || !workspace)
-    return set_error(TREX_E_ARG, "%s: null pointer argument", fn);
-  if ((sub_codes == nullptr) == (sub_rows == nullptr))
-    return set_error(TREX_E_ARG, "%s: exactly one of %s and sub_rows must be given", fn, sub_name);
-  if (workspace_bytes < trex_attach_workspace_bytes(B, L, n_all, Q))
-    return set_error(TREX_E_ARG, "%s: workspace too small", fn);
-  AttachArgs<LT> A;
-  nni_fill(A.n, attach_plan, leaves, cost, B, L, n_all, Q, tau, dp, const_cast<float*>(outside));
-  A.n.part = static_cast<double*>(workspace);
-  A.sub_codes = sub_codes;
-  A.sub_rows = sub_rows;
-  hipStream_t st = (hipStream_t)stream;
-  attach_launch(tau > 0.0f, st, A, weights);
-  if (int e = hip_check(fn)) return e;
-  reduce_partials(st, A.n.part, B, A.n.tiles, n_all, attach_score);
-  return hip_check(fn);
+int attach_run(const PassCall<LT>& c, const char* sub_name, const LT* sub_codes,
+               const float* sub_rows) {
+  return run_pass(
+      c, c.outside && c.score && c.workspace,
+      [&](int64_t& need) {
+        if ((sub_codes == nullptr) == (sub_rows == nullptr))
+          return set_error(TREX_E_ARG, "%s: exactly one of %s and sub_rows must be given", c.fn,
+                           sub_name);
+        need = trex_attach_workspace_bytes(c.B, c.L, c.n_all, c.Q);
+        return TREX_OK;
+      },
+      attach_moves(c.n_all), [&](const PassArgs<LT>& A, hipStream_t st) {
+        const AttachArgs<LT> AA{A, sub_codes, sub_rows};
+        with_variant(c.Q, c.tau > 0.0f, c.weights != nullptr, [&](auto v) {
+          using V = decltype(v);
+          hipLaunchKernelGGL((attach_score_kernel<LT, V::QP, V::DYN, V::SOFT, V::WT>),
+                             dim3(A.B * A.tiles), dim3(kWave), 0, st, AA, c.weights);
+        });
+      });
 }
 
 }  // namespace

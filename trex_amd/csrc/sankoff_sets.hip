@@ -2,7 +2,9 @@
 // bit mask of the states it allows at that site, its inside row 0 where the
 // bit is set and 1e5 elsewhere.  Mask 1 << c is code c, mask 0 is code -1
 // (all 1e5), (1 << Q) - 1 is missing data (all 0); bits at or above Q are
-// never looked at.
+// never looked at.  Owns trex_sankoff_sets_fwd and its workspace size,
+// trex_sankoff_sets_outside, trex_sankoff_sets_nni_w and
+// trex_sankoff_sets_attach_w (trex_sankoff_sets_spr_w is in sankoff_spr.hip).
 //
 // The forward pass is a kernel of its own in the shape of the outside pass
 // (sankoff_rows.h): one 64-lane wave takes 64 consecutive sites of ONE tree,
@@ -18,8 +20,12 @@ namespace trex {
 
 namespace {
 
+// The forward's record: the common one (plan: the attach plan) with site_score
+// where a pass with an outside table has that, and hard_root behind it.  It
+// keeps this layout of its own because moving site_score behind the common
+// part changed the padded kernels' SGPR spill counts (PERFLOG.md).
 struct SetsFwdArgs {
-  const int* plan;  // the attach plan's per-tree regions (past the header)
+  const int* plan;
   const int32_t* leaves;
   const float* cost;
   float* dp;
@@ -28,6 +34,10 @@ struct SetsFwdArgs {
   int B, L, nl, ni, Q, tiles;
   float a, bcoef;
   int hard_root;
+  SetsFwdArgs(const PassArgs<int32_t>& A, float* site_score_, int hard_root_)
+      : plan(A.plan), leaves(A.leaves), cost(A.cost), dp(const_cast<float*>(A.dp)),
+        site_score(site_score_), part(A.part), B(A.B), L(A.L), nl(A.nl), ni(A.ni), Q(A.Q),
+        tiles(A.tiles), a(A.a), bcoef(A.bcoef), hard_root(hard_root_) {}
 };
 
 template <int QP, bool DYN, bool SOFT>
@@ -64,13 +74,6 @@ __global__ __launch_bounds__(kWave) void sets_fwd_kernel(const SetsFwdArgs A) {
   if (lane == 0) A.part[blockIdx.x] = t;
 }
 
-template <int QP, bool DYN>
-void sets_fwd_launch_q(bool soft, hipStream_t st, const SetsFwdArgs& A) {
-  const dim3 grid(A.B * A.tiles), block(kWave);
-  if (soft) hipLaunchKernelGGL((sets_fwd_kernel<QP, DYN, true>), grid, block, 0, st, A);
-  else hipLaunchKernelGGL((sets_fwd_kernel<QP, DYN, false>), grid, block, 0, st, A);
-}
-
 }  // namespace
 
 }  // namespace trex
@@ -78,8 +81,7 @@ void sets_fwd_launch_q(bool soft, hipStream_t st, const SetsFwdArgs& A) {
 using namespace trex;
 
 extern "C" int64_t trex_sets_fwd_workspace_bytes(int B, int L, int n_all, int Q) {
-  if (B <= 0 || L <= 0 || n_all < 5 || n_all % 2 == 0 || Q < 2 || Q > kSiteMaxQ) return 0;
-  return (int64_t)B * ((L + kWave - 1) / kWave) * 8 + 256;
+  return partials_workspace_bytes(B, L, n_all, Q, 1);  // one entry, the tree's score
 }
 
 extern "C" int trex_sankoff_sets_fwd(const int32_t* attach_plan, const int32_t* leaf_sets,
@@ -87,48 +89,33 @@ extern "C" int trex_sankoff_sets_fwd(const int32_t* attach_plan, const int32_t* 
                                      unsigned flags, float* dp, float* site_score,
                                      float* tree_score, void* workspace, int64_t workspace_bytes,
                                      void* stream) {
-  const char* fn = "trex_sankoff_sets_fwd";
-  if (int e = nni_check_shape(fn, B, L, n_all, Q, tau)) return e;
-  if (!attach_plan || !leaf_sets || !cost || !dp || !tree_score || !workspace)
-    return set_error(TREX_E_ARG, "%s: null pointer argument", fn);
-  if (flags & ~TREX_FLAG_HARD_ROOT)
-    return set_error(TREX_E_ARG, "%s: unknown flags 0x%x", fn, flags);
-  if (workspace_bytes < trex_sets_fwd_workspace_bytes(B, L, n_all, Q))
-    return set_error(TREX_E_ARG, "%s: workspace too small", fn);
-  SetsFwdArgs A;
-  A.plan = attach_plan + TREX_PLAN_HEADER_INTS;
-  A.leaves = leaf_sets;
-  A.cost = cost;
-  A.dp = dp;
-  A.site_score = site_score;
-  A.part = static_cast<double*>(workspace);
-  A.B = B;
-  A.L = L;
-  A.nl = (n_all + 1) / 2;
-  A.ni = n_all - A.nl;
-  A.Q = Q;
-  A.tiles = (L + kWave - 1) / kWave;
-  tau_coefs(tau, &A.a, &A.bcoef);
-  A.hard_root = (flags & TREX_FLAG_HARD_ROOT) ? 1 : 0;
-  hipStream_t st = (hipStream_t)stream;
-  const bool soft = tau > 0.0f;
-  switch (Q) {
-    case 2: sets_fwd_launch_q<2, false>(soft, st, A); break;
-    case 3: sets_fwd_launch_q<3, false>(soft, st, A); break;
-    case 4: sets_fwd_launch_q<4, false>(soft, st, A); break;
-    default: sets_fwd_launch_q<kNniPadQ, true>(soft, st, A); break;
-  }
-  if (int e = hip_check(fn)) return e;
-  reduce_partials(st, A.part, B, A.tiles, 1, tree_score);
-  return hip_check(fn);
+  const PassCall<int32_t> c{"trex_sankoff_sets_fwd", attach_plan, leaf_sets, cost, B, L, n_all, Q,
+                            tau, dp, nullptr, nullptr, tree_score, workspace, workspace_bytes,
+                            stream};
+  return run_pass(
+      c, tree_score && workspace,
+      [&](int64_t& need) {
+        if (flags & ~TREX_FLAG_HARD_ROOT)
+          return set_error(TREX_E_ARG, "%s: unknown flags 0x%x", c.fn, flags);
+        need = trex_sets_fwd_workspace_bytes(B, L, n_all, Q);
+        return TREX_OK;
+      },
+      1, [&](const PassArgs<int32_t>& A, hipStream_t st) {
+        const SetsFwdArgs FA(A, site_score, (flags & TREX_FLAG_HARD_ROOT) ? 1 : 0);
+        with_variant(Q, tau > 0.0f, false, [&](auto v) {
+          using V = decltype(v);
+          hipLaunchKernelGGL((sets_fwd_kernel<V::QP, V::DYN, V::SOFT>), dim3(A.B * A.tiles),
+                             dim3(kWave), 0, st, FA);
+        });
+      });
 }
 
 extern "C" int trex_sankoff_sets_outside(const int32_t* nni_plan, const int32_t* leaf_sets,
                                          const float* cost, int B, int L, int n_all, int Q,
                                          float tau, const float* dp, float* outside,
                                          void* stream) {
-  return outside_run("trex_sankoff_sets_outside", nni_plan, leaf_sets, cost, B, L, n_all, Q, tau,
-                     dp, outside, stream);
+  return outside_run<int32_t>({"trex_sankoff_sets_outside", nni_plan, leaf_sets, cost, B, L, n_all,
+                               Q, tau, dp, outside, nullptr, nullptr, nullptr, 0, stream});
 }
 
 extern "C" int trex_sankoff_sets_nni_w(const int32_t* nni_plan, const int32_t* leaf_sets,
@@ -136,8 +123,9 @@ extern "C" int trex_sankoff_sets_nni_w(const int32_t* nni_plan, const int32_t* l
                                        float tau, const float* dp, const float* outside,
                                        const float* weights, float* nni_score, void* workspace,
                                        int64_t workspace_bytes, void* stream) {
-  return nni_run("trex_sankoff_sets_nni_w", nni_plan, leaf_sets, cost, B, L, n_all, Q, tau, dp,
-                 outside, weights, nni_score, workspace, workspace_bytes, stream);
+  return nni_run<int32_t>({"trex_sankoff_sets_nni_w", nni_plan, leaf_sets, cost, B, L, n_all, Q,
+                           tau, dp, const_cast<float*>(outside), weights, nni_score, workspace,
+                           workspace_bytes, stream});
 }
 
 extern "C" int trex_sankoff_sets_attach_w(const int32_t* attach_plan, const int32_t* leaf_sets,
@@ -147,7 +135,8 @@ extern "C" int trex_sankoff_sets_attach_w(const int32_t* attach_plan, const int3
                                           const float* weights, float* attach_score,
                                           void* workspace, int64_t workspace_bytes,
                                           void* stream) {
-  return attach_run("trex_sankoff_sets_attach_w", "sub_sets", attach_plan, leaf_sets, cost, B, L,
-                    n_all, Q, tau, dp, outside, sub_sets, sub_rows, weights, attach_score,
-                    workspace, workspace_bytes, stream);
+  return attach_run<int32_t>({"trex_sankoff_sets_attach_w", attach_plan, leaf_sets, cost, B, L,
+                              n_all, Q, tau, dp, const_cast<float*>(outside), weights,
+                              attach_score, workspace, workspace_bytes, stream},
+                             "sub_sets", sub_sets, sub_rows);
 }

@@ -21,8 +21,9 @@
 // a node is in subtree(v) or on the path, and so which table a row comes
 // from, is decided with scalar compares (wave-uniform).  Site scores are
 // summed over the wave in fp64 (fixed butterfly), lane 0 writes the per-tile
-// partials, nni_reduce_kernel adds the tiles in order.  The entries of moves
-// that do not exist get +inf partials on every call.
+// partials, reduce_partials_kernel adds the tiles in order.  The entries of
+// moves that do not exist get +inf partials on every call.  Owns
+// trex_spr_workspace_bytes, trex_sankoff_spr_w and trex_sankoff_sets_spr_w.
 #include <climits>
 
 #include "sankoff_rows.h"
@@ -32,8 +33,7 @@ namespace trex {
 namespace {
 
 template <class LT>
-struct SprArgs {
-  NniArgs<LT> n;   // n.plan: the SPR plan's per-tree regions; n.part: [B * tiles][n_all - 1][n_all]
+struct SprArgs : PassArgs<LT> {
   float* scratch;  // [B * tiles][ni][64][Q]
 };
 
@@ -66,7 +66,7 @@ __device__ __forceinline__ void msg(const CostM<QP, DYN>& cm, float a, float bco
 template <class LT, int QP, bool DYN, bool SOFT, bool WT>
 __global__ __launch_bounds__(kWave) void spr_score_kernel(const SprArgs<LT> SA,
                                                           const float* weights) {
-  const NniArgs<LT>& A = SA.n;
+  const PassArgs<LT>& A = SA;
   const int lane = threadIdx.x;
   const int b = blockIdx.x / A.tiles, tile = blockIdx.x % A.tiles;
   const int l = tile * kWave + lane;
@@ -197,43 +197,17 @@ __global__ __launch_bounds__(kWave) void spr_score_kernel(const SprArgs<LT> SA,
   }
 }
 
-template <class LT, int QP, bool DYN, bool SOFT>
-void spr_score_launch(hipStream_t st, const SprArgs<LT>& A, const float* w) {
-  const dim3 grid(A.n.B * A.n.tiles), block(kWave);
-  if (w)
-    hipLaunchKernelGGL((spr_score_kernel<LT, QP, DYN, SOFT, true>), grid, block, 0, st, A, w);
-  else
-    hipLaunchKernelGGL((spr_score_kernel<LT, QP, DYN, SOFT, false>), grid, block, 0, st, A, w);
-}
-
-template <class LT, int QP, bool DYN>
-void spr_launch_q(bool soft, hipStream_t st, const SprArgs<LT>& A, const float* w) {
-  if (soft) spr_score_launch<LT, QP, DYN, true>(st, A, w);
-  else spr_score_launch<LT, QP, DYN, false>(st, A, w);
-}
-
-template <class LT>
-void spr_launch(bool soft, hipStream_t st, const SprArgs<LT>& A, const float* w) {
-  switch (A.n.Q) {
-    case 2: spr_launch_q<LT, 2, false>(soft, st, A, w); break;
-    case 3: spr_launch_q<LT, 3, false>(soft, st, A, w); break;
-    case 4: spr_launch_q<LT, 4, false>(soft, st, A, w); break;
-    default: spr_launch_q<LT, kNniPadQ, true>(soft, st, A, w); break;
-  }
-}
-
 // bytes of the per-tile partials, rounded up to 256 (the scratch rows start
 // there); false when a size does not fit int64 / the entry count an int
 bool spr_sizes(int B, int L, int n_all, int Q, int64_t* part_bytes, int64_t* total) {
-  const int64_t waves = (int64_t)B * ((L + kWave - 1) / kWave);
-  const int64_t moves = (int64_t)(n_all - 1) * n_all, ni = tree_ni(n_all);
+  const int64_t nw = (int64_t)B * tiles(L), moves = spr_moves(n_all);
   int64_t part, scr;
   if (moves > INT_MAX || (int64_t)B * moves > 0x7FFFFFFFLL * 256) return false;
-  if (__builtin_mul_overflow(waves, moves * 8, &part) ||
+  if (__builtin_mul_overflow(nw, moves * 8, &part) ||
       __builtin_add_overflow(part, (int64_t)255, &part))
     return false;
   part = part / 256 * 256;
-  if (__builtin_mul_overflow(waves, ni * kWave * Q * 4, &scr) ||
+  if (__builtin_mul_overflow(nw, (int64_t)tree_ni(n_all) * kWave * Q * 4, &scr) ||
       __builtin_add_overflow(part, scr, total) ||
       __builtin_add_overflow(*total, (int64_t)256, total))
     return false;
@@ -242,27 +216,25 @@ bool spr_sizes(int B, int L, int n_all, int Q, int64_t* part_bytes, int64_t* tot
 }
 
 template <class LT>
-int spr_run(const char* fn, const int32_t* spr_plan, const LT* leaves, const float* cost, int B,
-            int L, int n_all, int Q, float tau, const float* dp, const float* outside,
-            const float* weights, float* spr_score, void* workspace, int64_t workspace_bytes,
-            void* stream) {
-  if (int e = nni_check_shape(fn, B, L, n_all, Q, tau)) return e;
-  if (!spr_plan || !leaves || !cost || !dp || !outside || !spr_score || !workspace)
-    return set_error(TREX_E_ARG, "%s: null pointer argument", fn);
-  int64_t part_bytes, total;
-  if (!spr_sizes(B, L, n_all, Q, &part_bytes, &total))
-    return set_error(TREX_E_UNSUPPORTED, "%s: B=%d L=%d n_all=%d: the score table or the "
-                     "workspace is too large", fn, B, L, n_all);
-  if (workspace_bytes < total) return set_error(TREX_E_ARG, "%s: workspace too small", fn);
-  SprArgs<LT> A;
-  nni_fill(A.n, spr_plan, leaves, cost, B, L, n_all, Q, tau, dp, const_cast<float*>(outside));
-  A.n.part = static_cast<double*>(workspace);
-  A.scratch = reinterpret_cast<float*>(static_cast<char*>(workspace) + part_bytes);
-  hipStream_t st = (hipStream_t)stream;
-  spr_launch(tau > 0.0f, st, A, weights);
-  if (int e = hip_check(fn)) return e;
-  reduce_partials(st, A.n.part, B, A.n.tiles, (n_all - 1) * n_all, spr_score);
-  return hip_check(fn);
+int spr_run(const PassCall<LT>& c) {
+  int64_t part_bytes = 0;
+  return run_pass(
+      c, c.outside && c.score && c.workspace,
+      [&](int64_t& need) {
+        if (!spr_sizes(c.B, c.L, c.n_all, c.Q, &part_bytes, &need))
+          return set_error(TREX_E_UNSUPPORTED, "%s: B=%d L=%d n_all=%d: the score table or the "
+                           "workspace is too large", c.fn, c.B, c.L, c.n_all);
+        return TREX_OK;
+      },
+      (int)spr_moves(c.n_all), [&](const PassArgs<LT>& A, hipStream_t st) {
+        const SprArgs<LT> SA{
+            A, reinterpret_cast<float*>(static_cast<char*>(c.workspace) + part_bytes)};
+        with_variant(c.Q, c.tau > 0.0f, c.weights != nullptr, [&](auto v) {
+          using V = decltype(v);
+          hipLaunchKernelGGL((spr_score_kernel<LT, V::QP, V::DYN, V::SOFT, V::WT>),
+                             dim3(A.B * A.tiles), dim3(kWave), 0, st, SA, c.weights);
+        });
+      });
 }
 
 }  // namespace
@@ -272,10 +244,8 @@ int spr_run(const char* fn, const int32_t* spr_plan, const LT* leaves, const flo
 using namespace trex;
 
 extern "C" int64_t trex_spr_workspace_bytes(int B, int L, int n_all, int Q) {
-  if (B <= 0 || L <= 0 || n_all < 5 || n_all > 65535 || n_all % 2 == 0 || Q < 2 ||
-      Q > kSiteMaxQ)
-    return 0;
   int64_t part_bytes, total;
+  if (!workspace_shape_ok(B, L, n_all, Q) || n_all > 65535) return 0;
   return spr_sizes(B, L, n_all, Q, &part_bytes, &total) ? total : 0;
 }
 
@@ -284,8 +254,9 @@ extern "C" int trex_sankoff_spr_w(const int32_t* spr_plan, const int8_t* leaves,
                                   const float* dp, const float* outside, const float* weights,
                                   float* spr_score, void* workspace, int64_t workspace_bytes,
                                   void* stream) {
-  return spr_run("trex_sankoff_spr_w", spr_plan, leaves, cost, B, L, n_all, Q, tau, dp, outside,
-                 weights, spr_score, workspace, workspace_bytes, stream);
+  return spr_run<int8_t>({"trex_sankoff_spr_w", spr_plan, leaves, cost, B, L, n_all, Q, tau, dp,
+                          const_cast<float*>(outside), weights, spr_score, workspace,
+                          workspace_bytes, stream});
 }
 
 extern "C" int trex_sankoff_sets_spr_w(const int32_t* spr_plan, const int32_t* leaf_sets,
@@ -293,6 +264,7 @@ extern "C" int trex_sankoff_sets_spr_w(const int32_t* spr_plan, const int32_t* l
                                        float tau, const float* dp, const float* outside,
                                        const float* weights, float* spr_score, void* workspace,
                                        int64_t workspace_bytes, void* stream) {
-  return spr_run("trex_sankoff_sets_spr_w", spr_plan, leaf_sets, cost, B, L, n_all, Q, tau, dp,
-                 outside, weights, spr_score, workspace, workspace_bytes, stream);
+  return spr_run<int32_t>({"trex_sankoff_sets_spr_w", spr_plan, leaf_sets, cost, B, L, n_all, Q,
+                           tau, dp, const_cast<float*>(outside), weights, spr_score, workspace,
+                           workspace_bytes, stream});
 }

@@ -158,15 +158,27 @@ class SankoffEngine:
                                    "_sets_attach_w): rebuild libtrexhip.so")
         return is_sets
 
-    def _sets_workspace(self):
-        """Per-tile partials of the state-set forward (no initialisation)."""
+    def _scratch(self, name):
+        """The uint8 workspace of pass ``name`` ("sets_fwd", "nni", "attach",
+        "spr"), trex_<name>_workspace_bytes long: kept in ``self._<name>_ws``,
+        grown when too small, never initialised."""
         p = self.plan
-        nbytes = lib().trex_sets_fwd_workspace_bytes(p.B, self.L, p.n_all, self.Q)
-        ws = getattr(self, "_sets_ws", None)
+        nbytes = getattr(lib(), f"trex_{name}_workspace_bytes")(p.B, self.L, p.n_all, self.Q)
+        ws = getattr(self, f"_{name}_ws", None)
         if ws is None or ws.numel() < max(nbytes, 1):
-            ws = self._sets_ws = _torch().empty(max(nbytes, 1), dtype=_torch().uint8,
-                                                device=self.device)
+            ws = _torch().empty(max(nbytes, 1), dtype=_torch().uint8, device=self.device)
+            setattr(self, f"_{name}_ws", ws)
         return ws
+
+    def _check_tensor(self, t, what, shape, dtype=None):
+        """``t`` is a contiguous tensor of ``shape`` and ``dtype`` (None:
+        float32) on the engine's device; ValueError naming it ``what``
+        otherwise."""
+        name = "float32" if dtype is None else str(dtype)
+        if (not hasattr(t, "dtype") or t.dtype != (dtype or _torch().float32)
+                or tuple(t.shape) != shape or not t.is_contiguous() or t.device != self.device):
+            raise ValueError(f"{what} must be a contiguous {name} {shape} tensor on the engine's "
+                             "device")
 
     def _check_weights(self, weights):
         """Site weights: a contiguous float32 (B, L) tensor on the engine's
@@ -175,13 +187,7 @@ class SankoffEngine:
         relative bar only when they are >= 0."""
         from ._lib import has_site_weights
 
-        torch = _torch()
-        shape = (self.plan.B, self.L)
-        if (not hasattr(weights, "dtype") or weights.dtype != torch.float32
-                or tuple(weights.shape) != shape or not weights.is_contiguous()
-                or weights.device != self.device):
-            raise ValueError(f"weights must be a contiguous float32 {shape} tensor on the "
-                             "engine's device")
+        self._check_tensor(weights, "weights", (self.plan.B, self.L))
         if not has_site_weights():
             raise RuntimeError(f"{lib()._name} has no site-weight entry points "
                                "(trex_site_weighted_sum, trex_sankoff_nni_w, "
@@ -197,17 +203,11 @@ class SankoffEngine:
         torch = _torch()
         self._check_weights(weights)
         B = self.plan.B
-        if (not hasattr(site_score, "dtype") or site_score.dtype != torch.float32
-                or tuple(site_score.shape) != (B, self.L) or not site_score.is_contiguous()
-                or site_score.device != self.device):
-            raise ValueError(f"site_score must be a contiguous float32 {(B, self.L)} tensor on "
-                             "the engine's device")
+        self._check_tensor(site_score, "site_score", (B, self.L))
         if out is None:
             out = torch.empty((B,), dtype=torch.float32, device=self.device)
-        elif (out.dtype != torch.float32 or tuple(out.shape) != (B,) or not out.is_contiguous()
-              or out.device != self.device):
-            raise ValueError(f"out must be a contiguous float32 {(B,)} tensor on the engine's "
-                             "device")
+        else:
+            self._check_tensor(out, "out", (B,))
         check(lib().trex_site_weighted_sum(ptr(site_score), ptr(weights), B, self.L, ptr(out),
                                            stream_handle(self.device)))
         return out
@@ -247,7 +247,7 @@ class SankoffEngine:
             ts = torch.empty((p.B,), dtype=torch.float32, device=self.device)
         flags = self._flags(hard_root)
         if is_sets:
-            ws = self._sets_workspace()
+            ws = self._scratch("sets_fwd")
             check(lib().trex_sankoff_sets_fwd(
                 ptr(p.attach_device(self.device)), ptr(leaves), ptr(cost), p.B, self.L, p.n_all,
                 self.Q, float(tau), flags, ptr(dp_t), ptr(ss), ptr(ts), ptr(ws), ws.numel(),
@@ -344,13 +344,29 @@ class SankoffEngine:
             self.Q, ptr(an), stream_handle(self.device)))
         return an
 
-    # -- NNI neighbour scores (sankoff_nni.hip) ------------------------------
+    # -- search passes (sankoff_rows.h, sankoff_nni / _sets / _spr.hip) ------
     def _check_table(self, t, what):
-        torch = _torch()
-        if (t is None or t.dtype != torch.float32 or tuple(t.shape) != self.dp_shape
-                or not t.is_contiguous() or t.device != self.device):
-            raise ValueError(f"{what} must be a contiguous float32 {self.dp_shape} tensor on the "
-                             "engine's device")
+        self._check_tensor(t, what, self.dp_shape)
+
+    def _scoring_tables(self, leaves, cost, tau, dp, outside, weights, also=None):
+        """What every scoring call starts with: the inputs checked (``also``:
+        the call's own argument check, run next), then ``(is_sets, dp,
+        outside)`` with the forward and / or the outside pass run for a table
+        that was not given."""
+        is_sets = self._check_inputs(leaves, cost, sets=True)
+        if weights is not None:
+            self._check_weights(weights)
+        if also is not None:
+            also()
+        if dp is None:
+            if outside is not None:
+                raise ValueError("outside without the dp table it was computed from")
+            dp = self.forward(leaves, cost, tau).dp
+        self._check_table(dp, "dp")
+        if outside is None:
+            outside = self.outside(leaves, cost, tau, dp)
+        self._check_table(outside, "outside")
+        return is_sets, dp, outside
 
     def outside(self, leaves, cost, tau: float, dp):
         """Outside table (B, n_int, L, Q) of ``dp`` (a forward's table at the
@@ -376,22 +392,9 @@ class SankoffEngine:
         All-ones weights give the bits of the unweighted call; the relative
         bar holds only for weights >= 0."""
         torch = _torch()
-        is_sets = self._check_inputs(leaves, cost, sets=True)
-        if weights is not None:
-            self._check_weights(weights)
+        is_sets, dp, outside = self._scoring_tables(leaves, cost, tau, dp, outside, weights)
         p = self.plan
-        if dp is None:
-            if outside is not None:
-                raise ValueError("outside without the dp table it was computed from")
-            dp = self.forward(leaves, cost, tau).dp
-        self._check_table(dp, "dp")
-        if outside is None:
-            outside = self.outside(leaves, cost, tau, dp)
-        self._check_table(outside, "outside")
-        nbytes = lib().trex_nni_workspace_bytes(p.B, self.L, p.n_all, self.Q)
-        ws = getattr(self, "_nni_ws", None)
-        if ws is None or ws.numel() < max(nbytes, 1):
-            ws = self._nni_ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=self.device)
+        ws = self._scratch("nni")
         score = torch.empty((p.B, p.n_int - 1, 2), dtype=torch.float32, device=self.device)
         head = (ptr(p.nni_device(self.device)), ptr(leaves), ptr(cost), p.B, self.L, p.n_all,
                 self.Q, float(tau), ptr(dp), ptr(outside))
@@ -415,31 +418,19 @@ class SankoffEngine:
         / ``outside`` are not given.  ``weights`` (float32 (B, L), finite):
         site weights as in ``nni_scores``."""
         torch = _torch()
-        is_sets = self._check_inputs(leaves, cost, sets=True)
-        if weights is not None:
-            self._check_weights(weights)
         p = self.plan
-        if (new_leaf is None) == (sub_rows is None):
-            raise ValueError("give exactly one of new_leaf and sub_rows")
-        sub, dtype, shape = ((new_leaf, leaves.dtype, (p.B, self.L)) if sub_rows is None else
-                             (sub_rows, torch.float32, (p.B, self.L, self.Q)))
-        if (not hasattr(sub, "dtype") or sub.dtype != dtype or tuple(sub.shape) != shape
-                or not sub.is_contiguous() or sub.device != self.device):
-            raise ValueError(f"{'new_leaf' if sub_rows is None else 'sub_rows'} must be a "
-                             f"contiguous {dtype} {shape} tensor on the engine's device")
-        if dp is None:
-            if outside is not None:
-                raise ValueError("outside without the dp table it was computed from")
-            dp = self.forward(leaves, cost, tau).dp
-        self._check_table(dp, "dp")
-        if outside is None:
-            outside = self.outside(leaves, cost, tau, dp)
-        self._check_table(outside, "outside")
-        nbytes = lib().trex_attach_workspace_bytes(p.B, self.L, p.n_all, self.Q)
-        ws = getattr(self, "_attach_ws", None)
-        if ws is None or ws.numel() < max(nbytes, 1):
-            ws = self._attach_ws = torch.empty(max(nbytes, 1), dtype=torch.uint8,
-                                               device=self.device)
+
+        def check_subtree():
+            if (new_leaf is None) == (sub_rows is None):
+                raise ValueError("give exactly one of new_leaf and sub_rows")
+            if sub_rows is None:
+                self._check_tensor(new_leaf, "new_leaf", (p.B, self.L), leaves.dtype)
+            else:
+                self._check_tensor(sub_rows, "sub_rows", (p.B, self.L, self.Q), torch.float32)
+
+        is_sets, dp, outside = self._scoring_tables(leaves, cost, tau, dp, outside, weights,
+                                                    check_subtree)
+        ws = self._scratch("attach")
         score = torch.empty((p.B, p.n_all), dtype=torch.float32, device=self.device)
         head = (ptr(p.attach_device(self.device)), ptr(leaves), ptr(cost), p.B, self.L, p.n_all,
                 self.Q, float(tau), ptr(dp), ptr(outside), ptr(new_leaf), ptr(sub_rows))
@@ -462,26 +453,13 @@ class SankoffEngine:
         pass when ``dp`` / ``outside`` are not given.  ``weights`` (float32
         (B, L), finite): site weights as in ``nni_scores``."""
         torch = _torch()
-        is_sets = self._check_inputs(leaves, cost, sets=True)
-        if weights is not None:
-            self._check_weights(weights)
         p = self.plan
-        plan_dev = p.spr_device(self.device)
-        if dp is None:
-            if outside is not None:
-                raise ValueError("outside without the dp table it was computed from")
-            dp = self.forward(leaves, cost, tau).dp
-        self._check_table(dp, "dp")
-        if outside is None:
-            outside = self.outside(leaves, cost, tau, dp)
-        self._check_table(outside, "outside")
-        nbytes = lib().trex_spr_workspace_bytes(p.B, self.L, p.n_all, self.Q)
-        ws = getattr(self, "_spr_ws", None)
-        if ws is None or ws.numel() < max(nbytes, 1):
-            ws = self._spr_ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=self.device)
+        is_sets, dp, outside = self._scoring_tables(leaves, cost, tau, dp, outside, weights,
+                                                    lambda: p.spr_device(self.device))
+        ws = self._scratch("spr")
         score = torch.empty((p.B, p.n_all - 1, p.n_all), dtype=torch.float32, device=self.device)
         fn = lib().trex_sankoff_sets_spr_w if is_sets else lib().trex_sankoff_spr_w
-        check(fn(ptr(plan_dev), ptr(leaves), ptr(cost), p.B, self.L, p.n_all, self.Q, float(tau),
+        check(fn(ptr(p.spr_device(self.device)), ptr(leaves), ptr(cost), p.B, self.L, p.n_all, self.Q, float(tau),
                  ptr(dp), ptr(outside), ptr(weights), ptr(score), ptr(ws), ws.numel(),
                  stream_handle(self.device)))
         return score

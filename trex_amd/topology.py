@@ -7,7 +7,6 @@ child of node ``j`` (src/trex/utils/types.py:30-35).  Leaves are
 
 from __future__ import annotations
 
-import functools
 
 import numpy as np
 
@@ -311,46 +310,43 @@ class TreePlan:
         self.n_dag_nodes = int(info[2])
         self.n_unreached = int(info[3])
         self._dev = {"plan": {}, "nni": {}, "attach": {}, "spr": {}}
+        self._search_host = {}  # the search plans built so far, by kind
 
-    # -- NNI plan (trex_nni_plan_build), built on first use ------------------
-    @functools.cached_property
-    def nni_host(self) -> np.ndarray:
-        """The NNI plan (include/trex_hip.h) as int32; TrexError
-        (TREX_E_TOPOLOGY) when a tree of the batch is not a proper rooted
-        binary tree of at least 3 leaves."""
-        return _build_plan("nni_plan", "NNI plan", self.children, self.B, self.n_all)
+    # -- the search plans (trex_{nni,attach,spr}_plan_build), built on first use --
+    def _search_plan(self, kind: str, device=None):
+        """The NNI / attach / SPR plan (include/trex_hip.h) as int32: the host
+        array, built once, or with ``device`` its copy there (cached per
+        device).  TrexError (TREX_E_TOPOLOGY) when a tree of the batch is not
+        a proper rooted binary tree of at least 3 leaves."""
+        host = self._search_host.get(kind)
+        if host is None:
+            if kind == "spr":
+                from ._lib import has_spr
+
+                if not has_spr():
+                    raise RuntimeError(f"{lib()._name} has no SPR entry points "
+                                       "(trex_spr_plan_build, trex_sankoff_spr_w, "
+                                       "trex_sankoff_sets_spr_w): rebuild libtrexhip.so")
+            what = {"nni": "NNI plan", "attach": "attach plan", "spr": "SPR plan"}[kind]
+            host = self._search_host[kind] = _build_plan(f"{kind}_plan", what, self.children,
+                                                         self.B, self.n_all)
+        return host if device is None else device_copy(self._dev[kind], host, device)
+
+    nni_host = property(lambda self: self._search_plan("nni"), doc="The NNI plan, int32.")
+    attach_host = property(lambda self: self._search_plan("attach"), doc="The attach plan, int32.")
+    spr_host = property(lambda self: self._search_plan("spr"), doc="The SPR plan, int32.")
 
     def nni_device(self, device):
         """The NNI plan as an int32 device tensor (cached per device)."""
-        return device_copy(self._dev["nni"], self.nni_host, device)
-
-    # -- attach plan (trex_attach_plan_build), built on first use -------------
-    @functools.cached_property
-    def attach_host(self) -> np.ndarray:
-        """The attach plan (include/trex_hip.h) as int32; TrexError as for
-        ``nni_host``."""
-        return _build_plan("attach_plan", "attach plan", self.children, self.B, self.n_all)
+        return self._search_plan("nni", device)
 
     def attach_device(self, device):
         """The attach plan as an int32 device tensor (cached per device)."""
-        return device_copy(self._dev["attach"], self.attach_host, device)
-
-    # -- SPR plan (trex_spr_plan_build), built on first use ------------------
-    @functools.cached_property
-    def spr_host(self) -> np.ndarray:
-        """The SPR plan (include/trex_hip.h) as int32; TrexError as for
-        ``nni_host``."""
-        from ._lib import has_spr
-
-        if not has_spr():
-            raise RuntimeError(f"{lib()._name} has no SPR entry points (trex_spr_plan_build, "
-                               "trex_sankoff_spr_w, trex_sankoff_sets_spr_w): rebuild "
-                               "libtrexhip.so")
-        return _build_plan("spr_plan", "SPR plan", self.children, self.B, self.n_all)
+        return self._search_plan("attach", device)
 
     def spr_device(self, device):
         """The SPR plan as an int32 device tensor (cached per device)."""
-        return device_copy(self._dev["spr"], self.spr_host, device)
+        return self._search_plan("spr", device)
 
     @property
     def nni_table(self) -> np.ndarray:
