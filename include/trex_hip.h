@@ -803,6 +803,66 @@ int trex_sankoff_sets_spr_w(const int32_t* spr_plan, const int32_t* leaf_sets, c
                             const float* outside, const float* weights, float* spr_score,
                             void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Per-branch changes: what happens on every edge of every tree of the batch,
+ * from the same dp and outside tables.  c is any node but the root, p its
+ * parent, s its sibling; i is p's state and j is c's (the orientation of
+ * C[i][j]).  Per site the joint cost of the pair is
+ *   J[i][j] = O_p[i] + M_s[i] + C[i][j] + D_c[j],    (+)_ij J = the site score
+ * (D_c of a leaf: its row as everywhere -- a code, a state set, an
+ * out-of-range code = all 1e5).  With w_l the site's weight (1 without):
+ *   tau > 0   counts[c][i][j] = sum_l w_l P_l[i][j], P_l[i][j] =
+ *             exp(-(J[i][j] - min J) / tau) / (sum over i, j of the same): the
+ *             Gibbs posterior of the pair, normalised by the site's own sum,
+ *             so sum_ij counts[c] = sum_l w_l.  Summed over the edges it is
+ *             the d_cost of trex_sankoff_bwd.
+ *   tau = 0   counts[c][i][j] = sum_l w_l [state_p = i][state_c = j] along the
+ *             reconstruction `states` (int8 [B][n_int][L], the layout of
+ *             trex_sankoff_backtrack's anc_states).  A leaf child's state is
+ *             the first-index argmin over j of C[state_p][j] + D_c[j].  A site
+ *             whose states value is outside [0, Q) at p or at an internal c
+ *             adds nothing to that edge.
+ *             length_min[c] / length_max[c] = sum_l w_l (min / max) of C[i][j]
+ *             over the pairs with J[i][j] == min J: the least and the largest
+ *             length of the branch over all most-parsimonious reconstructions.
+ *             J is formed in fp32 from the fp32 tables and the test is fp32
+ *             equality: exact for integer and dyadic costs; for other costs
+ *             the ties are the ones fp32 sees.
+ *   lengths[c] = sum_ij counts[c][i][j] C[i][j], formed from the fp64 sums
+ *             before they are rounded.
+ * counts fp32 [B][n_all][Q][Q]; lengths, length_min, length_max fp32
+ * [B][n_all], all indexed by the child's node id; the root's entries are
+ * written as 0.  Every entry is written by every call.
+ * trex_sankoff_edge_changes_w / trex_sankoff_sets_edge_changes_w (int8 codes /
+ *   int32 masks) take the attach plan.  weights may be NULL.  tau > 0: states,
+ *   length_min and length_max must be NULL; tau = 0: all three must be given;
+ *   anything else is TREX_E_ARG.  Shapes, the Q <= 20 limit (TREX_E_UNSUPPORTED
+ *   above it), the tau check and the 2 GiB table limit are those of
+ *   trex_sankoff_nni_w; every check runs before any launch and a refused call
+ *   writes nothing.  Sums over sites are fp64 in a fixed order (wave, tile
+ *   partials, tiles in order): repeated calls are bitwise equal and all-ones
+ *   weights give the bits of the unweighted call.
+ *   workspace >= trex_edge_workspace_bytes bytes = B tiles n_all (Q Q + 2) 8
+ *   (tiles = ceil(L / 64): per-tile fp64 partials), no initialisation needed
+ *   and nothing in it is read before it is written.  trex_edge_workspace_bytes
+ *   returns 0 for a shape the calls refuse, or when one tree's entry count
+ *   tiles n_all (Q Q + 2) exceeds 2^31 - 1 (the calls: TREX_E_UNSUPPORTED).
+ * Added without a version bump (trex_version() stays 10).
+ * ---------------------------------------------------------------------- */
+int64_t trex_edge_workspace_bytes(int B, int L, int n_all, int Q);
+int trex_sankoff_edge_changes_w(const int32_t* attach_plan, const int8_t* leaves,
+                                const float* cost, int B, int L, int n_all, int Q, float tau,
+                                const float* dp, const float* outside, const int8_t* states,
+                                const float* weights, float* counts, float* lengths,
+                                float* length_min, float* length_max, void* workspace,
+                                int64_t workspace_bytes, void* stream);
+int trex_sankoff_sets_edge_changes_w(const int32_t* attach_plan, const int32_t* leaf_sets,
+                                     const float* cost, int B, int L, int n_all, int Q, float tau,
+                                     const float* dp, const float* outside, const int8_t* states,
+                                     const float* weights, float* counts, float* lengths,
+                                     float* length_min, float* length_max, void* workspace,
+                                     int64_t workspace_bytes, void* stream);
+
 /* ========================================================================
  * Synthetic data on the device: trex's
  * generate_groundtruth (src/trex/ground_truth.py:112-197, mutate :20-52) and

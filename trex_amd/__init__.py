@@ -8,6 +8,7 @@ land, ``trex.tree``) on top of hand-written HIP kernels for gfx950 in
 from ._lib import LIB_PATH, TrexError, lib  # noqa: F401
 from .leafsets import encode_alignment, sets_from_codes  # noqa: F401
 from .sankoff import (  # noqa: F401
+    EdgeChanges,
     SankoffEngine,
     backtrack_sankoff_jit,
     leaf_codes,
@@ -27,6 +28,7 @@ from .search import (  # noqa: F401
     bootstrap_weights,
     clade_support,
     compress_sites,
+    describe_trees,
     nni_hill_climb,
     parsimony_ratchet,
     parsimony_search,
@@ -42,6 +44,7 @@ from .topology import (  # noqa: F401
     insert_leaf,
     random_topologies,
     relabel_leaves,
+    to_newick,
 )
 
 __all__ = [
@@ -53,4 +56,5 @@ __all__ = [
     "parsimony_search", "SearchResult", "compress_sites", "parsimony_ratchet", "RatchetResult",
     "bootstrap_weights", "bootstrap_search", "BootstrapResult", "clade_support",
     "sets_from_codes", "encode_alignment", "apply_spr", "spr_hill_climb",
+    "EdgeChanges", "describe_trees", "to_newick",
 ]

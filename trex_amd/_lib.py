@@ -86,6 +86,12 @@ SIGNATURES = {
                                   _c_i64, _p]),
     "trex_sankoff_sets_spr_w": (_c_i, [_p, _p, _p, _c_i, _c_i, _c_i, _c_i, _c_f, _p, _p, _p, _p,
                                        _p, _c_i64, _p]),
+    # per-branch change counts and branch lengths (OPTIONAL below)
+    "trex_edge_workspace_bytes": (_c_i64, [_c_i, _c_i, _c_i, _c_i]),
+    "trex_sankoff_edge_changes_w": (_c_i, [_p, _p, _p, _c_i, _c_i, _c_i, _c_i, _c_f, _p, _p, _p,
+                                           _p, _p, _p, _p, _p, _p, _c_i64, _p]),
+    "trex_sankoff_sets_edge_changes_w": (_c_i, [_p, _p, _p, _c_i, _c_i, _c_i, _c_i, _c_f, _p, _p,
+                                                _p, _p, _p, _p, _p, _p, _p, _c_i64, _p]),
     # multi-GPU exchange (RCCL, dlopen'ed on first use)
     "trex_comm_unique_id_bytes": (_c_i, []),
     "trex_comm_get_unique_id": (_c_i, [_p]),
@@ -183,7 +189,7 @@ SIGNATURES = {
 # entry points added without a version bump: a library named by TREX_HIP_LIB
 # may be an older v10 build without them (tools/ab.sh runs a parent commit's
 # library under this package); has_fused4(), has_site_weights(),
-# has_leaf_sets() and has_spr() tell
+# has_leaf_sets(), has_spr() and has_edge_changes() tell
 _FUSED4 = ("trex_fused4_program_ints", "trex_fused4_program_build", "trex_sankoff_fwd_bwd_prog")
 _SITE_WEIGHTS = ("trex_site_weighted_sum", "trex_sankoff_nni_w", "trex_sankoff_attach_w")
 _LEAF_SETS = ("trex_sets_fwd_workspace_bytes", "trex_sankoff_sets_fwd",
@@ -191,7 +197,9 @@ _LEAF_SETS = ("trex_sets_fwd_workspace_bytes", "trex_sankoff_sets_fwd",
               "trex_sankoff_sets_attach_w")
 _SPR = ("trex_spr_plan_ints", "trex_spr_plan_build", "trex_spr_workspace_bytes",
         "trex_sankoff_spr_w", "trex_sankoff_sets_spr_w")
-OPTIONAL = _FUSED4 + _SITE_WEIGHTS + _LEAF_SETS + _SPR
+_EDGES = ("trex_edge_workspace_bytes", "trex_sankoff_edge_changes_w",
+          "trex_sankoff_sets_edge_changes_w")
+OPTIONAL = _FUSED4 + _SITE_WEIGHTS + _LEAF_SETS + _SPR + _EDGES
 
 
 def has_fused4() -> bool:
@@ -212,6 +220,11 @@ def has_leaf_sets() -> bool:
 def has_spr() -> bool:
     """The loaded library has the SPR plan and scoring entry points."""
     return all(hasattr(lib(), name) for name in _SPR)
+
+
+def has_edge_changes() -> bool:
+    """The loaded library has the per-branch change entry points."""
+    return all(hasattr(lib(), name) for name in _EDGES)
 
 
 class TrexError(RuntimeError):

@@ -61,12 +61,20 @@ class ForwardResult:
     site_score: "object"  # (B, L) float32 or None
 
 
+@dataclass
+class EdgeChanges:
+    counts: "object"  # (B, n_all, Q, Q) float32: [b, child node, parent state, child state]
+    lengths: "object"  # (B, n_all) float32: sum_ij counts * cost
+    length_min: "object"  # (B, n_all) float32, tau = 0; None at tau > 0
+    length_max: "object"  # (B, n_all) float32, tau = 0; None at tau > 0
+
+
 class SankoffEngine:
     """Batched Sankoff for a fixed (topology batch, L, Q): the hot path.
 
     leaves: int8 (B, n_leaves, L) codes on the device; cost: float32 (Q, Q).
-    ``forward``, ``outside``, ``nni_scores``, ``attach_scores`` and ``spr_scores`` also take
-    int32 leaves: state sets, bit j of a cell = state j is allowed there
+    ``forward``, ``outside``, ``nni_scores``, ``attach_scores``, ``spr_scores`` and
+    ``edge_changes`` also take int32 leaves: state sets, bit j of a cell = state j is allowed there
     (``sets_from_codes``, ``encode_alignment``; DESIGN.md "State-set leaves";
     Q <= 20, proper rooted binary trees).  The adjoint has no state-set form.
     Everything is enqueued on torch's current stream; nothing synchronises.
@@ -160,7 +168,7 @@ class SankoffEngine:
 
     def _scratch(self, name):
         """The uint8 workspace of pass ``name`` ("sets_fwd", "nni", "attach",
-        "spr"), trex_<name>_workspace_bytes long: kept in ``self._<name>_ws``,
+        "spr", "edge"), trex_<name>_workspace_bytes long: kept in ``self._<name>_ws``,
         grown when too small, never initialised."""
         p = self.plan
         nbytes = getattr(lib(), f"trex_{name}_workspace_bytes")(p.B, self.L, p.n_all, self.Q)
@@ -463,6 +471,70 @@ class SankoffEngine:
                  ptr(dp), ptr(outside), ptr(weights), ptr(score), ptr(ws), ws.numel(),
                  stream_handle(self.device)))
         return score
+
+    def edge_changes(self, leaves, cost, tau: float = 0.0, *, dp=None, outside=None, states=None,
+                     weights=None) -> EdgeChanges:
+        """What happens on every branch (DESIGN.md "Per-branch changes"):
+        ``EdgeChanges(counts (B, n_all, Q, Q), lengths (B, n_all), length_min,
+        length_max)``, indexed by the branch's lower (child) node id;
+        ``counts[b, c, i, j]`` has the parent's state i first, as ``cost[i,
+        j]``; the root's entries are 0.
+
+        tau > 0: ``counts`` are the posterior expected numbers of sites (site
+        weights) with the pair of states (i, j) on the branch -- their sum
+        over the branches is ``value_and_grad``'s ``d_cost``; ``length_min``
+        and ``length_max`` are None and ``states`` must not be given.
+
+        tau = 0: ``counts`` follow the reconstruction ``states`` (int8 (B,
+        n_int, L), default ``self.backtrack(cost, dp)``); a leaf takes the
+        cheapest state its cell allows under its parent's state (first index
+        on ties); a site with a value outside [0, Q) in ``states`` is left out
+        of the branches that touch that node.  ``length_min`` / ``length_max``
+        are the branch's least and largest length over ALL most-parsimonious
+        reconstructions: a branch with ``length_max == 0`` is unsupported.
+        They compare fp32 sums for equality: exact for integer and dyadic
+        costs; for other costs the ties are the ones fp32 sees.
+
+        ``lengths = sum_ij counts * cost``.  Leaves are int8 codes or int32
+        state sets.  Runs the forward and / or the outside pass when ``dp`` /
+        ``outside`` are not given.  ``weights`` (float32 (B, L), finite): site
+        weights as in ``nni_scores``.  Sums over sites are fp64 in a fixed
+        order: repeated calls are bitwise equal."""
+        from ._lib import has_edge_changes
+
+        torch = _torch()
+        p = self.plan
+        hard = not tau > 0.0
+
+        def check_states():
+            if not has_edge_changes():
+                raise RuntimeError(f"{lib()._name} has no per-branch change entry points "
+                                   "(trex_sankoff_edge_changes_w, "
+                                   "trex_sankoff_sets_edge_changes_w): rebuild libtrexhip.so")
+            if states is None:
+                return
+            if not hard:
+                raise ValueError("states are a tau = 0 reconstruction; at tau > 0 the counts are "
+                                 "posterior expectations")
+            self._check_tensor(states, "states", (p.B, p.n_int, self.L), torch.int8)
+
+        is_sets, dp, outside = self._scoring_tables(leaves, cost, tau, dp, outside, weights,
+                                                    check_states)
+        if hard and states is None:
+            states = self.backtrack(cost, dp)
+        ws = self._scratch("edge")
+
+        def new(*shape):
+            return torch.empty(shape, dtype=torch.float32, device=self.device)
+
+        counts, lengths = new(p.B, p.n_all, self.Q, self.Q), new(p.B, p.n_all)
+        lmin, lmax = (new(p.B, p.n_all), new(p.B, p.n_all)) if hard else (None, None)
+        fn = lib().trex_sankoff_sets_edge_changes_w if is_sets else lib().trex_sankoff_edge_changes_w
+        check(fn(ptr(p.attach_device(self.device)), ptr(leaves), ptr(cost), p.B, self.L, p.n_all,
+                 self.Q, float(tau), ptr(dp), ptr(outside), ptr(states), ptr(weights),
+                 ptr(counts), ptr(lengths), ptr(lmin), ptr(lmax), ptr(ws), ws.numel(),
+                 stream_handle(self.device)))
+        return EdgeChanges(counts, lengths, lmin, lmax)
 
     def value_and_grad(self, leaves, cost, tau: float = 0.0, d_tree_score=None,
                        hard_root=False):

@@ -78,13 +78,10 @@ def _site_weights(weights, B, L, device):
     return w.contiguous()
 
 
-def _hill_climb(neighbours, apply_move, children, leaves, cost, tau, min_gain, max_rounds, device,
-                weights) -> HillClimbResult:
-    """The steepest-descent climb ``nni_hill_climb`` and ``spr_hill_climb``
-    share.  ``neighbours(eng, leaves, cost, tau, dp, weights)``: the scores of
-    every tree's neighbours, (B, ...) with the moves on the trailing axes;
-    ``apply_move(children, nl, n_all, i)``: one tree after its move of
-    flattened index i."""
+def _tree_inputs(children, leaves, cost, device, weights):
+    """What a function on a batch of given trees starts with: ``(device, ch
+    (B, n_all, 2) int32 copy, leaves (B, n_leaves, L) on the device, cost (Q,
+    Q) float32 on the device, weights (B, L) on the device or None)``."""
     torch = _torch()
     device = torch.device(device) if device is not None else _default_device()
     ch = np.array(children, dtype=np.int32, copy=True)
@@ -100,14 +97,39 @@ def _hill_climb(neighbours, apply_move, children, leaves, cost, tau, min_gain, m
     if lv.ndim != 3 or tuple(lv.shape[:2]) != (B, nl):
         raise ValueError(f"leaves must be ({B}, {nl}, L) or ({nl}, L), got {tuple(lv.shape)}")
     lv = lv.contiguous()
-    L = int(lv.shape[2])
     c = torch.as_tensor(cost).to(device=device, dtype=torch.float32).contiguous()
     if c.ndim != 2 or c.shape[0] != c.shape[1]:
         raise ValueError(f"cost must be (Q, Q), got {tuple(c.shape)}")
-    Q = int(c.shape[0])
+    return device, ch, lv, c, _site_weights(weights, B, int(lv.shape[2]), device)
+
+
+def describe_trees(children, leaves, cost, *, tau: float = 0.0, weights=None, device=None):
+    """Per-branch change counts and branch lengths of given trees, one call
+    from child lists to ``SankoffEngine.edge_changes``' ``EdgeChanges``
+    (device tensors indexed by the branch's child node id).  ``children``,
+    ``leaves``, ``cost`` and ``weights`` as for ``nni_hill_climb``.  tau = 0:
+    the counts follow the engine's own backtrack, and a branch whose
+    ``length_max`` is 0 has length 0 in every most-parsimonious reconstruction
+    (unsupported: it can be collapsed).  ``topology.to_newick`` writes a tree
+    with ``lengths[b]`` on its branches."""
+    device, ch, lv, c, w = _tree_inputs(children, leaves, cost, device, weights)
+    eng = SankoffEngine(TreePlan(ch), int(lv.shape[2]), int(c.shape[0]), device)
+    return eng.edge_changes(lv, c, tau, weights=w)
+
+
+def _hill_climb(neighbours, apply_move, children, leaves, cost, tau, min_gain, max_rounds, device,
+                weights) -> HillClimbResult:
+    """The steepest-descent climb ``nni_hill_climb`` and ``spr_hill_climb``
+    share.  ``neighbours(eng, leaves, cost, tau, dp, weights)``: the scores of
+    every tree's neighbours, (B, ...) with the moves on the trailing axes;
+    ``apply_move(children, nl, n_all, i)``: one tree after its move of
+    flattened index i."""
+    device, ch, lv, c, w = _tree_inputs(children, leaves, cost, device, weights)
+    B, n_all, _ = ch.shape
+    nl = (n_all + 1) // 2
+    L, Q = int(lv.shape[2]), int(c.shape[0])
     if not min_gain >= 0.0:
         raise ValueError("min_gain must be >= 0")
-    w = _site_weights(weights, B, L, device)
 
     def forward(ch_now):
         eng = SankoffEngine(TreePlan(ch_now), L, Q, device)

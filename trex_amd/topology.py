@@ -260,6 +260,42 @@ def relabel_leaves(children, perm) -> np.ndarray:
     return _renumber(kids, n_all - 1, leaf_id, lambda node: leaf_id.get(node, node))
 
 
+def to_newick(children, names=None, lengths=None, support=None, fmt="%g") -> str:
+    """One proper rooted binary tree's child lists (n_all, 2) as a Newick
+    string, ``(...);``.  Children are written in stored order.  ``names``:
+    the leaves' labels (default: their ids), written as given.  ``lengths``
+    (n_all,), indexed by node id as ``SankoffEngine.edge_changes``' outputs:
+    ``:length`` behind every node but the root.  ``support`` (n_int,), what
+    ``clade_support`` returns: the internal nodes' labels, the root's
+    included.  Numbers are written with ``fmt``.  ValueError for child lists
+    that are not a proper rooted binary tree (``insert_leaf``'s rule)."""
+    kids, nl, n_all = _proper_kids(children)
+    if names is None:
+        names = [str(x) for x in range(nl)]
+    if len(names) != nl:
+        raise ValueError(f"names must have {nl} entries, got {len(names)}")
+    if lengths is not None:
+        lengths = np.asarray(lengths, dtype=np.float64)
+        if lengths.shape != (n_all,):
+            raise ValueError(f"lengths must be ({n_all},), got {lengths.shape}")
+    if support is not None:
+        support = np.asarray(support, dtype=np.float64)
+        if support.shape != (n_all - nl,):
+            raise ValueError(f"support must be ({n_all - nl},), got {support.shape}")
+    text = {}
+    for node in range(n_all):  # children come before their parents
+        if node < nl:
+            s = str(names[node])
+        else:
+            s = "(" + ",".join(text.pop(c) for c in kids[node]) + ")"
+            if support is not None:
+                s += fmt % support[node - nl]
+        if lengths is not None and node != n_all - 1:
+            s += ":" + fmt % lengths[node]
+        text[node] = s
+    return text[n_all - 1] + ";"
+
+
 def _build_plan(name: str, what: str, children: np.ndarray, B: int, n_all: int,
                 *info) -> np.ndarray:
     """trex_<name>_ints, an int32 buffer of that size, trex_<name>_build into
